@@ -6,7 +6,14 @@ gathered to rank 0 over RCCL and re-interleaved into the frame.
 `value` = rays traced by all ranks (primary + shadow) / max-over-ranks time.
 
     python bench.py [--gpus N --steps K --warmup W --config c3 --orbit 0.01]
+    python bench.py --full [...]          the same, then every other figure and check
+    python bench.py --dump-outputs DIR    also writes the last timed frame to DIR/frame.npy
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets the scene up, warms up, times the K steps and prints the result line.  --full
+adds, untimed and after the timed steps, what takes runs of its own: the batch check, one frame
+per launch, the multi-rank frame checks, one frame alone, the synchronous host boundary, the CPU
+baseline and parity, the stream-copy rate and the roofline passes.
 
 `--gpus N` without a torch.distributed environment starts torch.distributed.run with N
 ranks as a child process (before anything touches the GPU) and passes rank 0's JSON
@@ -45,6 +52,16 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=500)   # 0.2 s of frames: steady state, not clock ramp-up
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline figure: the batch check, "
+                         "one frame per launch, the frame checks of the multi-rank path, one frame alone, the "
+                         "synchronous host boundary, the CPU baseline and parity, the stream-copy rate and the "
+                         "roofline passes.  Without it the run sets up, warms up, times the steps and prints the "
+                         "result line (`roofline` and `cpu_baseline` are null)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the last timed frame, as rank 0 holds it, to DIR/frame.npy: "
+                         "float32 (height, width, 4), the four bytes of every packed pixel; a frame over the "
+                         "size cap as a fixed seeded sample of its pixels, their indices in DIR/frame_pixels.npy")
     ap.add_argument("--orbit", type=float, default=0.0,
                     help="moving camera: add_rotate(ORBIT, 0) radians per frame, as the reference's mouse "
                          "drag does (RayTracer.cpp:553-565); 0 = the static default camera")
@@ -94,7 +111,7 @@ def parse_args(argv=None):
                          "(clock ramp-up after the idle scene setup)")
     ap.add_argument("--max-extra-warmup", type=int, default=4096, help="cap on the time-based extra warm-up frames")
     ap.add_argument("--frame-check", default="final", choices=["final", "every"],
-                    help="N > 1 / --dist: final = every frame rank 0 holds at the end is compared with its own "
+                    help="N > 1 / --dist, with --full: final = every frame rank 0 holds at the end is compared with its own "
                          "one-rank render of that frame's camera; every = also a checksum of every presented frame, "
                          "taken when rank 0 saw it complete (ipc exchange)")
     ap.add_argument("--sync-timeout-ms", type=int, default=10000,
@@ -120,7 +137,10 @@ def parse_args(argv=None):
                          "hardware queue each, beside torch's and RCCL's streams); 0 = keep the inherited value")
     ap.add_argument("--probe-launch", action="store_true",
                     help="launcher check without a GPU: every rank joins a gloo group and rank 0 reports the world")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full and (args.frame_check == "every" or args.inject_fault == "wrong-bands"):
+        ap.error("--frame-check every and --inject-fault wrong-bands need the frame check, which runs with --full")
+    return args
 
 
 def _free_port() -> int:
@@ -205,6 +225,31 @@ def jittered_cameras(p, w, h, n):
         dx, dy = halton(k, 2) - 0.5, halton(k, 3) - 0.5
         out[k, 8:11] = (q[2, :3] + q[0, :3] * (dx / w) + q[1, :3] * (dy / h)).astype(np.float32)
     return out
+
+
+DUMP_FULL_PIXELS = 4_000_000     # 16 B per pixel as float32 bytes: up to 64 MB dumped whole (1080p: 33 MB)
+DUMP_SAMPLE_PIXELS = 2_000_000   # a larger frame (4K): this many pixels, 24 B each with its index
+
+
+def dump_outputs(dirname, packed, w, h):
+    """--dump-outputs: a frame's packed pixels (one 32-bit word each) as DIR/frame.npy, float32, the
+    word's four bytes per pixel in memory order, shaped (h, w, 4) for a whole frame.  A frame of more
+    than DUMP_FULL_PIXELS pixels is written as a fixed sample (seeded: the same pixels every run) of
+    DUMP_SAMPLE_PIXELS rows, their pixel indices as float64 in DIR/frame_pixels.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    px = np.ascontiguousarray(packed).view(np.uint8).reshape(-1, 4)
+    index_file = os.path.join(dirname, "frame_pixels.npy")
+    if px.shape[0] > DUMP_FULL_PIXELS:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(px.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+        np.save(index_file, idx.astype(np.float64))
+        px = px[idx]
+    else:
+        if os.path.exists(index_file):   # of an earlier, sampled dump into this folder
+            os.remove(index_file)
+        if px.shape[0] == w * h:
+            px = px.reshape(h, w, 4)
+    np.save(os.path.join(dirname, "frame.npy"), px.astype(np.float32))
 
 
 _SYNC = []   # the run's rtamd.FrameSync (ipc exchange), for the failure report
@@ -545,7 +590,7 @@ def run(args, world, result_out=None):
     # the per-frame faults of the last rank (the set-up faults act elsewhere)
     fault = args.inject_fault in ("wrong-bands", "drop-put", "drop-put-warmup") and rank == world - 1 and world > 1
     fault_frame = 1 if args.inject_fault == "drop-put-warmup" else 4
-    check_every = use_dist and rank == 0 and args.frame_check == "every"
+    check_every = use_dist and rank == 0 and args.frame_check == "every"   # (parse_args: with --full only)
     sums = torch.zeros(nframes + args.max_extra_warmup, dtype=torch.int64, device=dev) if check_every else None
     sums_ptr = sums.data_ptr() if sums is not None else 0
     checksummed = []   # frame indices whose checksum was taken at their present (ipc exchange only)
@@ -575,6 +620,15 @@ def run(args, world, result_out=None):
     # rank 0's frame checks: its own one-rank render of a camera, and every frame a buffer set
     # holds against it (under --orbit every frame differs, so a band in the wrong frame shows)
     L = ptab.shape[0]
+    # Frame n renders camera cam_of(n): n % L in the warm-up, and (n - the frames of the time-based
+    # extra warm-up) % L from the first timed frame on, so the timed frames' cameras follow from
+    # --warmup and --steps alone and are the same from run to run (--dump-outputs)
+    cam_shift = [0]
+    timed_from = [1 << 62]
+
+    def cam_of(n):
+        return (n - cam_shift[0]) % L if n >= timed_from[0] else n % L
+
     sum_of = {}
     if use_dist and rank == 0 and not args.shard:
         full = torch.zeros(h * w, dtype=torch.int32, device=dev)
@@ -599,7 +653,7 @@ def run(args, world, result_out=None):
         ok = bool(held)
         held_bad.clear()
         for j, s in held:
-            reference(frame_of[j][s] % L)
+            reference(cam_of(frame_of[j][s]))
             if ipc:   # the uncached shared frame, copied out
                 rtamd.copy_device(got_frame.data_ptr(), put_dst[j][s], 4 * h * w, streams[0].cuda_stream)
                 torch.cuda.synchronize(dev)
@@ -719,10 +773,10 @@ def run(args, world, result_out=None):
             elif native:                 # likewise, through the rt_comm's events
                 slot_wait(j, sh[k])
         if FPL > 1:   # the batch's cameras; one launch renders them all when the batch is full
-            bcams[s] = orbit_params[n % len(orbit_params)] if orbit_params is not None else base_params
+            bcams[s] = orbit_params[(n - cam_shift[0]) % L] if orbit_params is not None else base_params
         else:
             if orbit_params is not None:   # updateCamera (RayTracer.cpp:609-672) for this frame
-                set_params(hdl, orbit_params[n % len(orbit_params)])
+                set_params(hdl, orbit_params[(n - cam_shift[0]) % L])
             launch(out_ptr[j][s], sh[k])
         frame_of[j][s] = n
         s += 1
@@ -825,6 +879,7 @@ def run(args, world, result_out=None):
             drain()
             warmup_frames += args.warmup
             torch.cuda.synchronize(dev)
+    cam_shift[0], timed_from[0] = warmup_frames - args.warmup, nstep[0]   # (cam_of: timed frame i has camera warmup + i)
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -840,6 +895,19 @@ def run(args, world, result_out=None):
     elapsed = time.perf_counter() - t0
     torch.cuda.set_stream(streams[0])
 
+    # --dump-outputs (untimed, before anything else renders into the buffer sets): the last timed
+    # frame as the timed path hands it to its caller: at N = 1 the packed pixels the launch wrote
+    # (with --shard this shard's bands), on the multi-rank path the frame rank 0 holds
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        j, s = next((j, s) for j in range(NB) for s in range(B) if frame_of[j][s] == nstep[0] - 1)
+        if ipc:   # the uncached shared frame, copied out
+            last = torch.empty(h * w, dtype=torch.int32, device=dev)
+            rtamd.copy_device(last.data_ptr(), put_dst[j][s], 4 * h * w, streams[0].cuda_stream)
+            torch.cuda.synchronize(dev)
+        else:
+            last = frames[j][s] if use_dist else outs[j][s][:npx]
+        dump_outputs(args.dump_outputs, last.cpu().numpy(), w, h)
+
     # per-launch kernel times of the timed steps, from the HIP events the library
     # records on the launch stream around each frame's kernels (ring of 64 frames)
     frame_ms_avg, kernel_ms_avg = r.timing_average(min(args.steps, 64))
@@ -848,7 +916,7 @@ def run(args, world, result_out=None):
     # every frame they hold, rendered by a batch launch, equals a single rt_render_device frame
     # of its camera
     batch_check = None
-    if FPL > 1 and not use_dist:
+    if args.full and FPL > 1 and not use_dist:
         torch.cuda.synchronize(dev)
         one = torch.zeros(cap, dtype=torch.int32, device=dev)
         n_checked, batch_ok = 0, True
@@ -856,7 +924,7 @@ def run(args, world, result_out=None):
             for s_ in range(filled[j]):
                 if frame_of[j][s_] < 0:
                     continue
-                r.set_params(ptab[frame_of[j][s_] % ptab.shape[0]])
+                r.set_params(ptab[cam_of(frame_of[j][s_])])
                 r.render_device(w, h, depth, flags, one.data_ptr(), tiling=tiling, stream=streams[0].cuda_stream)
                 torch.cuda.synchronize(dev)
                 n_checked += 1
@@ -867,7 +935,7 @@ def run(args, world, result_out=None):
     # (untimed for `value`) the same frames one per launch (rt_render_device: what a caller that has
     # only one frame at a time to give can get with F frames in flight), same cameras, same streams
     one_per_launch = None
-    if FPL > 1 and not use_dist and not args.shard:
+    if args.full and FPL > 1 and not use_dist and not args.shard:
         nf = max(args.steps, 64)
         for cam in {i % L for i in range(32, nf + 32)}:
             rays_of(cam)   # counted before the timed frames
@@ -891,13 +959,12 @@ def run(args, world, result_out=None):
                           "how": "rt_render_device, one frame per launch, same cameras and streams (untimed for value)"}
 
     total_frames = warmup_frames + args.steps
-    # frame n was rendered with camera n % L (the orbit table wraps when the time-based
-    # warm-up ran past it; a static camera has L = 1)
+    # frame n was rendered with camera cam_of(n) (a static camera has L = 1)
     # rays of the timed frames (untimed: one aux render per distinct camera)
     if L > 1:
         rays_local = prim_local = 0
         for n in range(warmup_frames, total_frames):
-            a, b = rays_of(n % L)
+            a, b = rays_of(cam_of(n))
             rays_local += a
             prim_local += b
         r.set_params(ptab[0])
@@ -926,7 +993,7 @@ def run(args, world, result_out=None):
     # landing in the wrong frame, or overwriting a frame before it was presented, is caught.
     frame_ok = None
     frame_check = None
-    if use_dist and rank == 0 and not args.shard:
+    if args.full and use_dist and rank == 0 and not args.shard:
         held, frame_ok = check_held()
         frame_check = {"held_frames_checked": held, "held_frames_equal": frame_ok,
                        "distinct_cameras": min(L, total_frames)}
@@ -934,8 +1001,8 @@ def run(args, world, result_out=None):
             # only the frames presented over IPC carry a checksum (after a fall-back to the RCCL
             # gather no further checksums are taken)
             got = sums.cpu().numpy()
-            bad = [n for n in checksummed if int(got[n]) != sum_of.get(n % L, None) and
-                   int(got[n]) != reference(n % L)]
+            bad = [n for n in checksummed if int(got[n]) != sum_of.get(cam_of(n), None) and
+                   int(got[n]) != reference(cam_of(n))]
             frame_check.update({"presented_frames_checksummed": len(checksummed), "checksum_mismatches": len(bad),
                                 "mismatched_frames": bad[:16]})
             frame_ok = frame_ok and not bad
@@ -951,7 +1018,7 @@ def run(args, world, result_out=None):
     # nothing overlapping it -- the frame's critical path, which the frames in flight of the
     # timed region hide (C2: 0.25 ms alone against 0.08 ms per frame with four in flight)
     frame_latency = None
-    if world == 1 and not args.shard:
+    if args.full and world == 1 and not args.shard:
         lat = []
         for _ in range(21):
             t1 = time.perf_counter()
@@ -966,7 +1033,7 @@ def run(args, world, result_out=None):
             set_params(hdl, orbit_params[0])
 
     host_boundary = None
-    if world == 1 and not args.shard:
+    if args.full and world == 1 and not args.shard:
         def host_rate(buf_ptr, n=20):
             r.render_host_ptr(w, h, depth, flags, buf_ptr)
             t1 = time.perf_counter()
@@ -1008,183 +1075,186 @@ def run(args, world, result_out=None):
             dist.destroy_process_group()
         return
 
-    # ---- CPU oracle leg (rank 0): algorithmic record fetches per frame (roofline), the CPU
-    # baseline, and the parity check of an S_strict GPU frame against the oracle's ----
-    from oracle import oracle
-    scene = rtamd.Scene.from_mesh(mesh, bvh)
-    cpu = None
-    parity = None
-    budget = args.cpu_seconds if (world == 1 and not args.no_cpu_baseline) else min(args.cpu_seconds, 5.0)
-    ncores = host_threads
-    tprobe = time.perf_counter()
-    probe = oracle.render(scene, ptab[0], w, h, depth=depth, flags=flags, pixels=(0, (w * h) // 4093, 4093),
-                          nthreads=ncores, aux=False)
-    tprobe = time.perf_counter() - tprobe
-    per_px = tprobe / max(1, (w * h) // 4093)
-    npix_sample = int(min(w * h, max(1000, budget / max(per_px, 1e-9))))
-    stride = max(1, (w * h) // npix_sample)
-    npix_sample = (w * h) // stride
-    # the sample is repeated (whole frames when the frame is cheaper than the budget)
-    # until about `budget` seconds of CPU work have been timed
-    t0 = time.perf_counter()
-    reps = 0
-    while True:
-        samp = oracle.render(scene, ptab[0], w, h, depth=depth, flags=flags, pixels=(0, npix_sample, stride),
-                             nthreads=ncores, aux=False)
-        reps += 1
-        cpu_s = time.perf_counter() - t0
-        if cpu_s >= 0.6 * budget or reps >= 1000:
-            break
-    st = samp["stats"]
-    cpu_rays = sum(st[k]["rays"] for k in ("primary", "shadow", "secondary"))
-    kinds = [k for k in ("primary", "shadow", "secondary") if st[k]["rays"]]
-    # per traced ray (oracle, reference visit order): the reference layout's bytes (SURVEY.md
-    # 8d) and this layout's record fetches (one 64-B inner record per inner visit, one 48-B
-    # triangle record per triangle test; leaves cost none: their range is in the child ref)
-    bpr = sum(80.0 * st[k]["inner"] + 16.0 * st[k]["leaf"] + 64.0 * st[k]["tris"] for k in kinds) / max(1, cpu_rays)
-    rec_inner = sum(st[k]["inner"] for k in kinds) / max(1, cpu_rays)
-    rec_tri = sum(st[k]["tris"] for k in kinds) / max(1, cpu_rays)
-    if world == 1 and not args.no_cpu_baseline:
-        cpu = {"value": cpu_rays * reps / cpu_s / 1e6, "unit": "Mrays/s", "cores": ncores, "kind": "port",
-               "sample": f"oracle/rt_oracle.c on every {stride}th pixel of the same frame ({npix_sample} px, "
-                         f"{cpu_rays} rays) x {reps} repetition(s), {cpu_s:.1f} s, {ncores} threads = every "
-                         f"core this job may use ({cpu_share['source']}: affinity {cpu_share['affinity']} CPUs, "
-                         f"cgroup quota {cpu_share['cgroup_quota']}, os.cpu_count() {cpu_share['os_cpu_count']})",
-               "host_cpu_share": cpu_share}
-        if stride == 1:
-            # the oracle's frame against the GPU's frame in the oracle's arithmetic (S_strict),
-            # whole frame, same camera; the benched arithmetic is pinned to the reference
-            # kernel itself by tests/test_fullsize_gpu.py
-            r.set_params(ptab[0])
-            gpu = r.render(w, h, depth=depth, flags=(flags & ~2) | 64)
-            parity = {"mode": "S_strict (RT_FLAG_STRICT_MATH) vs oracle/rt_oracle.c", "pixels": int(w * h),
-                      "equal": bool(np.array_equal(gpu, samp["out"])),
-                      "differing_pixels": int(np.sum(gpu != samp["out"]))}
-
-    # measured device copy rate (the roofline also against a measured stream-copy
-    # peak): 1 GiB -> 1 GiB device-to-device copies, read + write bytes over HIP-event time
-    src = torch.empty(1 << 28, dtype=torch.float32, device=dev)
-    dst = torch.empty_like(src)
-    dst.copy_(src)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(10):
-        dst.copy_(src)
-    ev1.record()
-    ev1.synchronize()
-    stream_copy_gbs = 10 * 2 * src.numel() * 4 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
-    del src, dst
-
     frame_rays = rays_total / args.steps
-    frame_px = float(w * h) if not args.shard else float(npx)
-    alg_bytes = frame_rays * bpr + 4.0 * frame_px            # reference-layout bytes per frame
-    wavefront = depth > 1 and (flags & 8)
-    ns = {0: "rtk_ref", 64: "rtk_strict", 2: "rtk_hw"}[math_flags]
-    kname = (f"{ns}::first_bounce_batch_kernel<true, {'true' if depth > 1 else 'false'}>" if FPL > 1
-             else f"{ns}::first_bounce_kernel<true, {'true' if depth > 1 else 'false'}, 0>" if (depth == 1 or wavefront)
-             else f"{ns}::render_kernel<true>")
-    # ---- roofline.  The path is a gather of 48-56 B records; its time is set by
-    # the vector-memory path (TA/TD), not HBM (nodes and triangles are re-read from L1/L2/Infinity
-    # Cache).  That path merges the lanes of a quad that read the same record, and a load costs
-    # per distinct record per quad (scripts/gather_peak_sweep.py), so its unit of work is a quad
-    # request.  achieved = the frame's quad requests, counted on the GPU while rendering this
-    # frame with a counting instantiation of the same kernels (rt_fetch_counts, every launch of
-    # the frame), over ms_per_step; peak = the measured rate of quad requests when every
-    # lane reads a different record of an L2-resident table on every CU (rt_gather_peak).
-    # Both in 64-B record slots. ----
-    hbm = {"bytes_per_ray_reference_layout": round(bpr, 1),
-           "achieved_gbs": round(alg_bytes / (ms_per_step * 1e-3) / 1e9, 2), "peak_gbs": HBM_PEAK_GBS,
-           "note": "SURVEY 8d algorithmic bytes of the reference layout; exceeds HBM peak because the scene is "
-                   "served from L1/L2/Infinity Cache"}
-    roof = ft = None
-    fetch_cams = [0]
-    if (depth == 1 or wavefront) and not args.shard and not args.no_roofline:
-        # the timed frames' cameras (orbit: up to 8 spread over the timed frames, averaged)
-        timed = sorted({n % L for n in range(warmup_frames, total_frames)})
-        fetch_cams = [timed[i * len(timed) // min(8, len(timed))] for i in range(min(8, len(timed)))]
-        try:
-            fts = []
-            for cam in fetch_cams:
-                r.set_params(ptab[cam])
-                fts.append(r.fetch_counts(w, h, depth, flags & ~16))   # every launch of the frame, counted
-            ft = {k: sum(f[k] for f in fts) / len(fts) for k in fts[0]}
-        except rtamd.RtError as e:                           # e.g. a scene off the fast kernel
-            print(f"fetch counts unavailable: {e}", file=sys.stderr)
-            ft = None
-        r.set_params(ptab[0])
-    if ft is not None:
-        pk_ms, pk_n = r.gather_peak(16384, 256)          # 1 MiB table: L2-resident on every XCD
-        quads = ft["quad_inner"] + ft["quad_tri"]
-        # every lane a distinct record: one quad request per lane; at N > 1 every GPU's path
-        peak_rps = world * pk_n / (pk_ms * 1e-3)
-        ach_rps = quads / (ms_per_step * 1e-3)
-        roof = {"bound": "l2_gather", "unit": "GB/s",
-                "achieved": round(ach_rps * 64 / 1e9, 2), "peak": round(peak_rps * 64 / 1e9, 2),
-                "frac": round(ach_rps / peak_rps, 4), "traffic": None,
-                "roof": "quad record requests of the frame (counted on the GPU, every launch) vs random distinct "
-                        "records from an L2-resident table on every CU (rt_gather_peak)"
-                        + (f", x{world} GPUs" if world > 1 else ""),
-                "quad_requests_per_frame": quads, "lane_fetches_per_frame": ft["inner"] + ft["tri"],
-                "lanes_per_quad_request": round((ft["inner"] + ft["tri"]) / max(1, quads), 3),
-                "wave_distinct_records_per_frame": ft["distinct_inner"] + ft["distinct_tri"],
-                "inner_fetches": ft["inner"], "tri_fetches": ft["tri"], "distinct_inner": ft["distinct_inner"],
-                "distinct_tri": ft["distinct_tri"], "wave_iterations": ft["wave_instructions"],
-                "mixed_inner_tri_iterations": ft["mixed_instructions"],
-                "peak_records_per_s": round(peak_rps), "peak_ns_per_record_per_cu": None,
-                "fetch_counts_cameras": len(fetch_cams)}
-        cus = torch.cuda.get_device_properties(dev).multi_processor_count
-        roof["peak_ns_per_record_per_cu"] = round(world * cus / peak_rps * 1e9, 3)
-        # The latency roof: a traversal iteration is a dependent fetch, so a wave's
-        # iterations form a chain.  rt_chase_peak times one dependent traversal-shaped iteration of a
-        # wave with every wave slot of the chip (8 per SIMD) running such a chain through an L2-resident
-        # table, the lanes of a quad on one chain; the frame's wave iterations spread over those slots
-        # then take at least iterations / slots * that time.
-        ch_iters = 512
-        lat = {}
-        for grp in (4, 1, 64):
-            ch_ms, ch_waves = r.chase_peak(16384, ch_iters, grp)
-            lat[grp] = (ch_ms / ch_iters, ch_waves)
-        t_iter_ms, slots = lat[4]
-        model_ms = ft["wave_instructions"] / (world * slots) * t_iter_ms
-        roof["latency"] = {
-            "roof": "wave iterations of the frame (counted on the GPU) / wave slots x the time of one dependent "
-                    "traversal-shaped iteration at full occupancy (rt_chase_peak, quad-coherent chains, L2-resident)",
-            "wave_iterations_per_frame": ft["wave_instructions"], "wave_slots": world * slots,
-            "ns_per_dependent_iteration": round(t_iter_ms * 1e6, 1),
-            "ns_per_dependent_iteration_lane_distinct": round(lat[1][0] * 1e6, 1),
-            "ns_per_dependent_iteration_wave_uniform": round(lat[64][0] * 1e6, 1),
-            "model_ms": round(model_ms, 4), "frac": round(model_ms / ms_per_step, 4)}
-    if roof is None:   # the fused path, or --no-roofline: the HBM model of SURVEY 8d
-        roof = {"bound": "hbm", "unit": "GB/s", "achieved": hbm["achieved_gbs"], "peak": HBM_PEAK_GBS,
-                "frac": round(hbm["achieved_gbs"] / HBM_PEAK_GBS, 4), "traffic": None,
-                "roof": "HBM (no fetch counts for this run)"}
-    # HIP-event times of one timing entry = one launch group (FPL frames): per launch and per frame
-    roof.update({"hbm": hbm, "stream_copy_gbs": round(stream_copy_gbs, 1),
-                 "kernel_ms_per_launch": round(kernel_ms_avg, 4), "kernel_ms_per_frame": round(kernel_ms_avg / FPL, 4),
-                 "launch_kernels_ms": round(frame_ms_avg, 4), "launches_overlap": F > 1, "kernel": kname,
-                 "frames_per_launch": FPL,
-                 "records_per_ray_oracle": round(rec_inner + rec_tri, 2)})
-    # HBM traffic: PMC counters need rocprofv3, so they come from separate profiling runs of this
-    # command (scripts/pmc_c3.sh); the newest round's file is used and labelled as such, with the
-    # library build it measured -- stale if that is not the library this run loaded
-    pmc_files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]", f"pmc_{args.config}.json")))
-    if pmc_files and not args.orbit and not args.extra_flags:
-        try:
-            pj = json.load(open(pmc_files[-1]))
-            lib_now = rtamd.library_digest()
-            # per frame, like `achieved` (a launch of the batch kernel renders frames_per_launch frames)
-            roof["traffic"] = pj.get("hbm_bytes_per_frame", pj.get("hbm_bytes_per_launch"))
-            if pj.get("occupancy"):   # achieved waves per SIMD of the same kernel (PMC, separate run)
-                roof["occupancy"] = dict(pj["occupancy"], file=os.path.relpath(pmc_files[-1], ROOT),
-                                         stale=pj.get("library_digest") != rtamd.library_digest())
-            roof["traffic_source"] = {
-                "file": os.path.relpath(pmc_files[-1], ROOT),
-                "how": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (separate runs, not this "
-                       "process), FETCH_SIZE x2 per the guide",
-                "library_measured": pj.get("library_digest"), "library_now": lib_now,
-                "stale": pj.get("library_digest") != lib_now}
-        except (OSError, ValueError):
-            pass
+    # Everything below up to the result line is --full only: a plain run reports the headline figure
+    roof = cpu = parity = None
+    if args.full:
+        # ---- CPU oracle leg (rank 0): algorithmic record fetches per frame (roofline), the CPU
+        # baseline, and the parity check of an S_strict GPU frame against the oracle's ----
+        from oracle import oracle
+        scene = rtamd.Scene.from_mesh(mesh, bvh)
+        cpu = None
+        parity = None
+        budget = args.cpu_seconds if (world == 1 and not args.no_cpu_baseline) else min(args.cpu_seconds, 5.0)
+        ncores = host_threads
+        tprobe = time.perf_counter()
+        probe = oracle.render(scene, ptab[0], w, h, depth=depth, flags=flags, pixels=(0, (w * h) // 4093, 4093),
+                              nthreads=ncores, aux=False)
+        tprobe = time.perf_counter() - tprobe
+        per_px = tprobe / max(1, (w * h) // 4093)
+        npix_sample = int(min(w * h, max(1000, budget / max(per_px, 1e-9))))
+        stride = max(1, (w * h) // npix_sample)
+        npix_sample = (w * h) // stride
+        # the sample is repeated (whole frames when the frame is cheaper than the budget)
+        # until about `budget` seconds of CPU work have been timed
+        t0 = time.perf_counter()
+        reps = 0
+        while True:
+            samp = oracle.render(scene, ptab[0], w, h, depth=depth, flags=flags, pixels=(0, npix_sample, stride),
+                                 nthreads=ncores, aux=False)
+            reps += 1
+            cpu_s = time.perf_counter() - t0
+            if cpu_s >= 0.6 * budget or reps >= 1000:
+                break
+        st = samp["stats"]
+        cpu_rays = sum(st[k]["rays"] for k in ("primary", "shadow", "secondary"))
+        kinds = [k for k in ("primary", "shadow", "secondary") if st[k]["rays"]]
+        # per traced ray (oracle, reference visit order): the reference layout's bytes (SURVEY.md
+        # 8d) and this layout's record fetches (one 64-B inner record per inner visit, one 48-B
+        # triangle record per triangle test; leaves cost none: their range is in the child ref)
+        bpr = sum(80.0 * st[k]["inner"] + 16.0 * st[k]["leaf"] + 64.0 * st[k]["tris"] for k in kinds) / max(1, cpu_rays)
+        rec_inner = sum(st[k]["inner"] for k in kinds) / max(1, cpu_rays)
+        rec_tri = sum(st[k]["tris"] for k in kinds) / max(1, cpu_rays)
+        if world == 1 and not args.no_cpu_baseline:
+            cpu = {"value": cpu_rays * reps / cpu_s / 1e6, "unit": "Mrays/s", "cores": ncores, "kind": "port",
+                   "sample": f"oracle/rt_oracle.c on every {stride}th pixel of the same frame ({npix_sample} px, "
+                             f"{cpu_rays} rays) x {reps} repetition(s), {cpu_s:.1f} s, {ncores} threads = every "
+                             f"core this job may use ({cpu_share['source']}: affinity {cpu_share['affinity']} CPUs, "
+                             f"cgroup quota {cpu_share['cgroup_quota']}, os.cpu_count() {cpu_share['os_cpu_count']})",
+                   "host_cpu_share": cpu_share}
+            if stride == 1:
+                # the oracle's frame against the GPU's frame in the oracle's arithmetic (S_strict),
+                # whole frame, same camera; the benched arithmetic is pinned to the reference
+                # kernel itself by tests/test_fullsize_gpu.py
+                r.set_params(ptab[0])
+                gpu = r.render(w, h, depth=depth, flags=(flags & ~2) | 64)
+                parity = {"mode": "S_strict (RT_FLAG_STRICT_MATH) vs oracle/rt_oracle.c", "pixels": int(w * h),
+                          "equal": bool(np.array_equal(gpu, samp["out"])),
+                          "differing_pixels": int(np.sum(gpu != samp["out"]))}
+
+        # measured device copy rate (the roofline also against a measured stream-copy
+        # peak): 1 GiB -> 1 GiB device-to-device copies, read + write bytes over HIP-event time
+        src = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+        dst = torch.empty_like(src)
+        dst.copy_(src)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        for _ in range(10):
+            dst.copy_(src)
+        ev1.record()
+        ev1.synchronize()
+        stream_copy_gbs = 10 * 2 * src.numel() * 4 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9
+        del src, dst
+
+        frame_px = float(w * h) if not args.shard else float(npx)
+        alg_bytes = frame_rays * bpr + 4.0 * frame_px            # reference-layout bytes per frame
+        wavefront = depth > 1 and (flags & 8)
+        ns = {0: "rtk_ref", 64: "rtk_strict", 2: "rtk_hw"}[math_flags]
+        kname = (f"{ns}::first_bounce_batch_kernel<true, {'true' if depth > 1 else 'false'}>" if FPL > 1
+                 else f"{ns}::first_bounce_kernel<true, {'true' if depth > 1 else 'false'}, 0>" if (depth == 1 or wavefront)
+                 else f"{ns}::render_kernel<true>")
+        # ---- roofline.  The path is a gather of 48-56 B records; its time is set by
+        # the vector-memory path (TA/TD), not HBM (nodes and triangles are re-read from L1/L2/Infinity
+        # Cache).  That path merges the lanes of a quad that read the same record, and a load costs
+        # per distinct record per quad (scripts/gather_peak_sweep.py), so its unit of work is a quad
+        # request.  achieved = the frame's quad requests, counted on the GPU while rendering this
+        # frame with a counting instantiation of the same kernels (rt_fetch_counts, every launch of
+        # the frame), over ms_per_step; peak = the measured rate of quad requests when every
+        # lane reads a different record of an L2-resident table on every CU (rt_gather_peak).
+        # Both in 64-B record slots. ----
+        hbm = {"bytes_per_ray_reference_layout": round(bpr, 1),
+               "achieved_gbs": round(alg_bytes / (ms_per_step * 1e-3) / 1e9, 2), "peak_gbs": HBM_PEAK_GBS,
+               "note": "SURVEY 8d algorithmic bytes of the reference layout; exceeds HBM peak because the scene is "
+                       "served from L1/L2/Infinity Cache"}
+        roof = ft = None
+        fetch_cams = [0]
+        if (depth == 1 or wavefront) and not args.shard and not args.no_roofline:
+            # the timed frames' cameras (orbit: up to 8 spread over the timed frames, averaged)
+            timed = sorted({cam_of(n) for n in range(warmup_frames, total_frames)})
+            fetch_cams = [timed[i * len(timed) // min(8, len(timed))] for i in range(min(8, len(timed)))]
+            try:
+                fts = []
+                for cam in fetch_cams:
+                    r.set_params(ptab[cam])
+                    fts.append(r.fetch_counts(w, h, depth, flags & ~16))   # every launch of the frame, counted
+                ft = {k: sum(f[k] for f in fts) / len(fts) for k in fts[0]}
+            except rtamd.RtError as e:                           # e.g. a scene off the fast kernel
+                print(f"fetch counts unavailable: {e}", file=sys.stderr)
+                ft = None
+            r.set_params(ptab[0])
+        if ft is not None:
+            pk_ms, pk_n = r.gather_peak(16384, 256)          # 1 MiB table: L2-resident on every XCD
+            quads = ft["quad_inner"] + ft["quad_tri"]
+            # every lane a distinct record: one quad request per lane; at N > 1 every GPU's path
+            peak_rps = world * pk_n / (pk_ms * 1e-3)
+            ach_rps = quads / (ms_per_step * 1e-3)
+            roof = {"bound": "l2_gather", "unit": "GB/s",
+                    "achieved": round(ach_rps * 64 / 1e9, 2), "peak": round(peak_rps * 64 / 1e9, 2),
+                    "frac": round(ach_rps / peak_rps, 4), "traffic": None,
+                    "roof": "quad record requests of the frame (counted on the GPU, every launch) vs random distinct "
+                            "records from an L2-resident table on every CU (rt_gather_peak)"
+                            + (f", x{world} GPUs" if world > 1 else ""),
+                    "quad_requests_per_frame": quads, "lane_fetches_per_frame": ft["inner"] + ft["tri"],
+                    "lanes_per_quad_request": round((ft["inner"] + ft["tri"]) / max(1, quads), 3),
+                    "wave_distinct_records_per_frame": ft["distinct_inner"] + ft["distinct_tri"],
+                    "inner_fetches": ft["inner"], "tri_fetches": ft["tri"], "distinct_inner": ft["distinct_inner"],
+                    "distinct_tri": ft["distinct_tri"], "wave_iterations": ft["wave_instructions"],
+                    "mixed_inner_tri_iterations": ft["mixed_instructions"],
+                    "peak_records_per_s": round(peak_rps), "peak_ns_per_record_per_cu": None,
+                    "fetch_counts_cameras": len(fetch_cams)}
+            cus = torch.cuda.get_device_properties(dev).multi_processor_count
+            roof["peak_ns_per_record_per_cu"] = round(world * cus / peak_rps * 1e9, 3)
+            # The latency roof: a traversal iteration is a dependent fetch, so a wave's
+            # iterations form a chain.  rt_chase_peak times one dependent traversal-shaped iteration of a
+            # wave with every wave slot of the chip (8 per SIMD) running such a chain through an L2-resident
+            # table, the lanes of a quad on one chain; the frame's wave iterations spread over those slots
+            # then take at least iterations / slots * that time.
+            ch_iters = 512
+            lat = {}
+            for grp in (4, 1, 64):
+                ch_ms, ch_waves = r.chase_peak(16384, ch_iters, grp)
+                lat[grp] = (ch_ms / ch_iters, ch_waves)
+            t_iter_ms, slots = lat[4]
+            model_ms = ft["wave_instructions"] / (world * slots) * t_iter_ms
+            roof["latency"] = {
+                "roof": "wave iterations of the frame (counted on the GPU) / wave slots x the time of one dependent "
+                        "traversal-shaped iteration at full occupancy (rt_chase_peak, quad-coherent chains, L2-resident)",
+                "wave_iterations_per_frame": ft["wave_instructions"], "wave_slots": world * slots,
+                "ns_per_dependent_iteration": round(t_iter_ms * 1e6, 1),
+                "ns_per_dependent_iteration_lane_distinct": round(lat[1][0] * 1e6, 1),
+                "ns_per_dependent_iteration_wave_uniform": round(lat[64][0] * 1e6, 1),
+                "model_ms": round(model_ms, 4), "frac": round(model_ms / ms_per_step, 4)}
+        if roof is None:   # the fused path, or --no-roofline: the HBM model of SURVEY 8d
+            roof = {"bound": "hbm", "unit": "GB/s", "achieved": hbm["achieved_gbs"], "peak": HBM_PEAK_GBS,
+                    "frac": round(hbm["achieved_gbs"] / HBM_PEAK_GBS, 4), "traffic": None,
+                    "roof": "HBM (no fetch counts for this run)"}
+        # HIP-event times of one timing entry = one launch group (FPL frames): per launch and per frame
+        roof.update({"hbm": hbm, "stream_copy_gbs": round(stream_copy_gbs, 1),
+                     "kernel_ms_per_launch": round(kernel_ms_avg, 4), "kernel_ms_per_frame": round(kernel_ms_avg / FPL, 4),
+                     "launch_kernels_ms": round(frame_ms_avg, 4), "launches_overlap": F > 1, "kernel": kname,
+                     "frames_per_launch": FPL,
+                     "records_per_ray_oracle": round(rec_inner + rec_tri, 2)})
+        # HBM traffic: PMC counters need rocprofv3, so they come from separate profiling runs of this
+        # command (scripts/pmc_c3.sh); the newest round's file is used and labelled as such, with the
+        # library build it measured -- stale if that is not the library this run loaded
+        pmc_files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]", f"pmc_{args.config}.json")))
+        if pmc_files and not args.orbit and not args.extra_flags:
+            try:
+                pj = json.load(open(pmc_files[-1]))
+                lib_now = rtamd.library_digest()
+                # per frame, like `achieved` (a launch of the batch kernel renders frames_per_launch frames)
+                roof["traffic"] = pj.get("hbm_bytes_per_frame", pj.get("hbm_bytes_per_launch"))
+                if pj.get("occupancy"):   # achieved waves per SIMD of the same kernel (PMC, separate run)
+                    roof["occupancy"] = dict(pj["occupancy"], file=os.path.relpath(pmc_files[-1], ROOT),
+                                             stale=pj.get("library_digest") != rtamd.library_digest())
+                roof["traffic_source"] = {
+                    "file": os.path.relpath(pmc_files[-1], ROOT),
+                    "how": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (separate runs, not this "
+                           "process), FETCH_SIZE x2 per the guide",
+                    "library_measured": pj.get("library_digest"), "library_now": lib_now,
+                    "stale": pj.get("library_digest") != lib_now}
+            except (OSError, ValueError):
+                pass
 
     res = {
         "metric": METRIC,

@@ -10,7 +10,7 @@ for r in $(seq 1 "$reps"); do
     for v in $variants; do
       lib=real-time-opencl-raytracer_amd/lib/ab/$v/librtamd.so
       [ "$v" = main ] && lib=real-time-opencl-raytracer_amd/lib/librtamd.so
-      RTAMD_LIB=$PWD/$lib timeout -k 10 200 python bench.py --config "$c" --no-cpu-baseline "$@" \
+      RTAMD_LIB=$PWD/$lib timeout -k 10 200 python bench.py --full --config "$c" --no-cpu-baseline "$@" \
           > "gpurun_out/ab/${v}_${c}_${r}.json" 2> "gpurun_out/ab/${v}_${c}_${r}.err"
       rc=$?
       echo "$v $c $r rc=$rc $(grep -o '"ms_per_step": [0-9.]*' gpurun_out/ab/${v}_${c}_${r}.json)"

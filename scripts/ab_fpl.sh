@@ -5,7 +5,7 @@ mkdir -p gpurun_out/ab
 for r in 1 2; do
   for c in c2 c3 c4; do
     for f in 4 8; do
-      timeout -k 10 200 python bench.py --config $c --frames-per-launch $f --no-cpu-baseline --no-roofline --steps 480 \
+      timeout -k 10 200 python bench.py --full --config $c --frames-per-launch $f --no-cpu-baseline --no-roofline --steps 480 \
           > gpurun_out/ab/fpl${f}_${c}_${r}.json 2> gpurun_out/ab/fpl${f}_${c}_${r}.err || exit 1
     done
   done

@@ -13,7 +13,7 @@ for r in 1 2; do
       case $v in wf) fz=8;; b) lib=$PWD/real-time-opencl-raytracer_amd/lib/ab/b/librtamd.so;;
                  bf) fz=8; lib=$PWD/real-time-opencl-raytracer_amd/lib/ab/b/librtamd.so;;
                  w12f) fz=8; lib=$PWD/real-time-opencl-raytracer_amd/lib/ab/w12/librtamd.so;; esac
-      RTAMD_FREEZE_ORDER=$fz RTAMD_LIB=$lib timeout -k 10 200 python bench.py --config $c --no-cpu-baseline --no-roofline --steps 300 \
+      RTAMD_FREEZE_ORDER=$fz RTAMD_LIB=$lib timeout -k 10 200 python bench.py --full --config $c --no-cpu-baseline --no-roofline --steps 300 \
           > gpurun_out/ab/${v}_${c}_${r}.json 2> gpurun_out/ab/${v}_${c}_${r}.err || exit 1
     done
   done

@@ -11,7 +11,7 @@ for r in 1 2; do
       lib=$PWD/real-time-opencl-raytracer_amd/lib/librtamd.so; env=""
       [ $v = direct ] && env="RTAMD_HOST_FLUSH=0"
       [ $v = prev ] && lib=$PWD/real-time-opencl-raytracer_amd/lib/ab/prev/librtamd.so
-      env $env RTAMD_LIB=$lib timeout -k 10 200 python bench.py --config $c --no-cpu-baseline --no-roofline --steps 300 \
+      env $env RTAMD_LIB=$lib timeout -k 10 200 python bench.py --full --config $c --no-cpu-baseline --no-roofline --steps 300 \
           > gpurun_out/ab/${v}_${c}_${r}.json 2> gpurun_out/ab/${v}_${c}_${r}.err || exit 1
     done
   done

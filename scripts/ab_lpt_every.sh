@@ -8,7 +8,7 @@ for r in 1 2; do
     c=$spec; extra=""
     [ $spec = orbit ] && { c=c3; extra="--orbit 0.002"; }
     for k in 1 4 8 16; do
-      RTAMD_LPT_EVERY=$k timeout -k 10 200 python bench.py --config $c $extra --no-cpu-baseline --no-roofline --steps 300 \
+      RTAMD_LPT_EVERY=$k timeout -k 10 200 python bench.py --full --config $c $extra --no-cpu-baseline --no-roofline --steps 300 \
           > gpurun_out/ab/k${k}_${spec}_${r}.json 2> gpurun_out/ab/k${k}_${spec}_${r}.err || exit 1
     done
   done

@@ -10,7 +10,7 @@ for r in 1 2; do
     for v in s1 s2 s0 prev; do
       lib=$PWD/real-time-opencl-raytracer_amd/lib/librtamd.so; mode=1
       case $v in s2) mode=2;; s0) mode=0;; prev) lib=$PWD/real-time-opencl-raytracer_amd/lib/ab/prev/librtamd.so;; esac
-      RTAMD_STAGE_ROWS=$mode RTAMD_LIB=$lib timeout -k 10 200 python bench.py --config $c --no-cpu-baseline --no-roofline --steps 300 \
+      RTAMD_STAGE_ROWS=$mode RTAMD_LIB=$lib timeout -k 10 200 python bench.py --full --config $c --no-cpu-baseline --no-roofline --steps 300 \
           > gpurun_out/ab/${v}_${c}_${r}.json 2> gpurun_out/ab/${v}_${c}_${r}.err || exit 1
     done
   done

@@ -8,7 +8,7 @@ for r in $(seq 1 "$reps"); do
   for c in $configs; do
     for k in $ks; do
       o=gpurun_out/fpl/${c}_k${k}_$r
-      timeout -k 10 150 python bench.py --config "$c" --no-cpu-baseline --frames-per-launch "$k" "$@" > $o.json 2> $o.err
+      timeout -k 10 150 python bench.py --full --config "$c" --no-cpu-baseline --frames-per-launch "$k" "$@" > $o.json 2> $o.err
       rc=$?
       echo "$c K=$k rep $r rc=$rc $(grep -o '"ms_per_step": [0-9.]*' $o.json) $(grep -o '"batch_check": {[^}]*}' $o.json)"
       if [ $rc -ne 0 ]; then exit $rc; fi

@@ -19,6 +19,6 @@ i=0
 for set in "$@"; do
   i=$((i+1))
   timeout -k 10 180 rocprofv3 --pmc $set -d $out/p$i -o run --output-format csv -- \
-      python3 bench.py --steps 5 --warmup 1 --warmup-seconds 0 --no-cpu-baseline --no-roofline --inflight 1 $BENCH_ARGS > $out/p$i.log 2>&1 || { echo "pass $i failed"; exit 1; }
+      python3 bench.py --full --steps 5 --warmup 1 --warmup-seconds 0 --no-cpu-baseline --no-roofline --inflight 1 $BENCH_ARGS > $out/p$i.log 2>&1 || { echo "pass $i failed"; exit 1; }
 done
 python3 scripts/pmc_summary.py $out/p*

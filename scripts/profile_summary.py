@@ -20,6 +20,7 @@ import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.path.join(ROOT, os.environ.get("BENCH_OUT", "bench_out"))   # where scripts/profile_c3.sh wrote
 # C3 is depth 1: the single-bounce kernel (FASTONLY, no next ray, the product instantiation TR = 0),
 # or with bench.py's frames per launch > 1 (the depth-1 default) its batch form
 KERNEL_ONE = "first_bounce_kernel<true, false, 0>"
@@ -28,7 +29,7 @@ KERNEL = KERNEL_ONE
 
 
 def counter(d, name):
-    f = glob.glob(os.path.join(ROOT, "gpurun_out", d, "**", "*counter_collection.csv"), recursive=True)[0]
+    f = glob.glob(os.path.join(OUT, d, "**", "*counter_collection.csv"), recursive=True)[0]
     v = [float(r["Counter_Value"]) for r in csv.DictReader(open(f)) if KERNEL in r["Kernel_Name"]
          and r["Counter_Name"] == name]
     return statistics.median(v), len(v), f
@@ -44,7 +45,7 @@ def main():
     rnd = args[0] if len(args) > 0 else "r01"
     cfg = args[1] if len(args) > 1 else "c3"
     global KERNEL
-    tlog = os.path.join(ROOT, "gpurun_out", "prof_trace.log")
+    tlog = os.path.join(OUT, "prof_trace.log")
     fpl = 1
     if os.path.exists(tlog):
         j = json.loads([ln for ln in open(tlog) if ln.startswith("{")][-1])
@@ -57,7 +58,7 @@ def main():
         occ = json.load(open(occ_path))
     out = os.path.join(ROOT, "profiles", rnd)
     os.makedirs(out, exist_ok=True)
-    stats = glob.glob(os.path.join(ROOT, "gpurun_out", "prof_trace", "**", "*kernel_stats.csv"), recursive=True)[0]
+    stats = glob.glob(os.path.join(OUT, "prof_trace", "**", "*kernel_stats.csv"), recursive=True)[0]
     shutil.copy(stats, os.path.join(out, f"{cfg}_kernel_stats.csv"))
     avg_ns = None
     for r in csv.DictReader(open(stats)):
@@ -67,7 +68,7 @@ def main():
     # K timed frames, then bench.py's host-boundary renders; compare with the HIP-event
     # average bench.py printed for the same K frames
     timed_us = hip_ms = None
-    trace = glob.glob(os.path.join(ROOT, "gpurun_out", "prof_trace", "**", "*kernel_trace.csv"), recursive=True)
+    trace = glob.glob(os.path.join(OUT, "prof_trace", "**", "*kernel_trace.csv"), recursive=True)
     if trace and os.path.exists(tlog):
         rows = sorted((r for r in csv.DictReader(open(trace[0])) if KERNEL in r["Kernel_Name"]),
                       key=lambda r: int(r["Start_Timestamp"]))
@@ -84,7 +85,7 @@ def main():
     shutil.copy(ff, os.path.join(out, f"{cfg}_pmc_fetch.csv"))
     shutil.copy(fw, os.path.join(out, f"{cfg}_pmc_write.csv"))
     for log in ("prof_bench.log", "prof_trace.log"):
-        p = os.path.join(ROOT, "gpurun_out", log)
+        p = os.path.join(OUT, log)
         if os.path.exists(p):
             shutil.copy(p, os.path.join(out, f"{cfg}_{log.replace('prof_', '')}"))
     res = {

@@ -31,7 +31,7 @@ pytestmark = pytest.mark.gpu
                                      (11, ["--gather", "torch", "--frames-per-launch", "3"])])
 def test_bench_dist_path_assembles_the_frame(i, extra):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29611 + i))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dist", "--config", "c2", "--direct", "--steps", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dist", "--config", "c2", "--direct", "--steps", "4",
            "--warmup", "2", "--no-cpu-baseline", "--cpu-seconds", "0.5"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
     assert p.returncode == 0, _why(p)
@@ -46,7 +46,7 @@ def test_bench_dist_shard_diagnostic_completes(gather):
     """--dist --shard 0/8: rank 0's exchange work at N = 8 with one process behind it (the
     frame-sync block counts the processes that put, not the shards)."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29631 + (gather == "native")))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dist", "--shard", "0/8", "--gather", gather,
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dist", "--shard", "0/8", "--gather", gather,
            "--config", "c2", "--direct", "--steps", "8", "--warmup", "2", "--warmup-seconds", "0",
            "--no-cpu-baseline", "--sync-timeout-ms", "2000", "--hang-timeout", "100"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
@@ -68,7 +68,7 @@ def _why(p):
 def _ranks_on_one_gpu(n, extra, timeout=115):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--gather", "ipc", "--pg", "gloo",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n), "--gather", "ipc", "--pg", "gloo",
            "--config", "c2", "--direct", "--warmup", "2", "--warmup-seconds", "0", "--no-cpu-baseline",
            "--cpu-seconds", "0.5", "--hang-timeout", "100"] + extra   # the production exchange bound (10 s)
     return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)

@@ -12,8 +12,9 @@ import numpy as np
 import pytest
 
 import rtamd
+from conftest import reference_data
 
-CUBES2_DAE = "/root/reference/x64/Release/data/collada/cubes2.DAE"
+CUBES2_DAE = os.path.join(reference_data(), "collada", "cubes2.DAE")   # tests/golden/reference_data
 KEYS = ("vertices", "indices", "normals", "normals_indices", "materials", "tri_to_material", "scene_min", "scene_max")
 
 
@@ -32,7 +33,6 @@ def _same_as_oracle(path):
     return a
 
 
-@pytest.mark.skipif(not os.path.exists(CUBES2_DAE), reason="reference data not present")
 def test_reference_scene_cubes2_dae():
     a = _same_as_oracle(CUBES2_DAE)
     assert a["indices"].size // 3 == 23392

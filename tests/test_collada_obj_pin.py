@@ -31,16 +31,15 @@ import numpy as np
 import pytest
 
 import rtamd
+from conftest import reference_data
 
-DATA = "/root/reference/x64/Release/data"
+DATA = reference_data()   # tests/golden/reference_data, unpacked
 DAE = os.path.join(DATA, "collada", "cubes2.DAE")
 OBJ = os.path.join(DATA, "models", "cubes2.obj")
 INCH = 2.54
 POS_TOL = 0.01    # cm: OBJ prints 4 decimals; float32 at |x| ~ 2300 cm is 2.4e-4; t from printed values
 NRM_TOL = 2e-3    # OBJ prints unit normals with 4 decimals
 THREE_AXIS = {"ChamferBox005", "ChamferBox006"}
-
-pytestmark = pytest.mark.skipif(not (os.path.exists(DAE) and os.path.exists(OBJ)), reason="reference data not present")
 
 
 def _local(tag):

@@ -6,9 +6,10 @@ import numpy as np
 import pytest
 
 import rtamd
+from conftest import reference_data
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_DATA = "/root/reference/x64/Release/data"
+REF_DATA = reference_data()   # tests/golden/reference_data, unpacked
 
 
 def test_struct_sizes():
@@ -133,7 +134,6 @@ def test_mesh_from_arrays_validates():
         rtamd.Mesh.from_arrays(np.zeros((3, 4), np.float32), np.array([0, 1, 5], np.int32))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference assets not present")
 def test_obj_loader_reference_assets():
     m = rtamd.Mesh.load_obj(os.path.join(REF_DATA, "models", "cubes2.obj"))
     assert m.num_triangles == 23392

@@ -18,9 +18,10 @@ import numpy as np
 import pytest
 
 import rtamd
+from conftest import reference_data
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CUBES2 = "/root/reference/x64/Release/data/models/cubes2.obj"
+CUBES2 = os.path.join(reference_data(), "models", "cubes2.obj")   # tests/golden/reference_data
 DIGESTS = os.path.join(ROOT, "tests", "golden", "sbvh_digests.json")
 
 
@@ -101,7 +102,6 @@ def test_signed_zero_and_axis_planes():
     _same(m)
 
 
-@pytest.mark.skipif(not os.path.exists(CUBES2), reason="reference data not present")
 def test_oracle_pinned_by_survey_probe_on_cubes2():
     m = rtamd.Mesh.load_obj(CUBES2)
     nodes, refs = _same(m, threads=8)
@@ -110,7 +110,6 @@ def test_oracle_pinned_by_survey_probe_on_cubes2():
     assert digest(nodes, refs) == want
 
 
-@pytest.mark.skipif(not os.path.exists(CUBES2), reason="reference data not present")
 def test_traversal_work_pinned_by_survey_probe_on_cubes2():
     """The survey ran the REAL SplitBVHBuilder and the reference's traversal order on cubes2.obj
     at the reference's 1024x768 with its default camera (SURVEY.md 6 / BASELINE.md: 18.74 inner
