@@ -142,6 +142,41 @@ int rt_upload_scene(rt_ctx* ctx, const rt_float4* verts, int32_t nv, const int32
                     const rt_float4* normals, int32_t nnorm, const int32_t* normal_idx,
                     const rt_material* mats, int32_t nmat, const int32_t* tri_to_mat);
 
+/* Animated geometry.  The reference uploads its mesh once (initRayTrace,
+ * RayTracer.cpp:942-984) and then only moves the camera; a deforming mesh would have to refit its
+ * BVH_Node_ array and upload everything again.  Here the derived device records are rewritten in
+ * place from a new vertex buffer: the triangle and shading records, and the inner records' boxes
+ * by a bottom-up refit on the GPU.
+ *
+ * Refit semantics (host and device alike): a leaf with num_tris > 0 takes, per axis, the min and
+ * max over the three vertices of every triangle of its [offset_tris, +num_tris) range -- the whole
+ * triangle, also where an SBVH leaf held a clipped reference (conservative); a leaf with
+ * num_tris <= 0 keeps its box; an inner node takes the union of its children's boxes.  Min / max
+ * ignore a NaN operand (fminf / fmaxf); vertices are expected to be finite.  Only min.xyz / max.xyz
+ * of reachable nodes change.  A scene is refittable when every reachable node with
+ * offset_left >= 0 is a valid inner node and every reachable node has exactly one parent;
+ * otherwise RT_ERR_BAD_SCENE (the message names the node) and nothing is modified.
+ *
+ * rt_refit_nodes: the CPU refit of a caller's node array, in place (no context, no GPU): keeps
+ *   host arrays, a BVH cache or another rank's upload in step with rt_update_vertices.
+ * rt_update_vertices / rt_update_vertices_device: new vertices (and normals, or NULL to keep
+ *   them) for the uploaded scene, from host memory / from device memory produced on `stream`
+ *   (NULL = the null stream).  nv (and nnorm with normals) must equal the upload's.  Synchronous:
+ *   waits for the frames in flight, runs on the context's stream, returns when the records are
+ *   rewritten.  Afterwards the scene is the one rt_upload_scene would build from the new vertices
+ *   and the rt_refit_nodes nodes.  Needs a scene from rt_upload_scene that is refittable
+ *   (rt_scene_image_load and rt_scene_copy keep no refit data): else RT_ERR_BAD_SCENE.
+ * rt_scene_bounds: the root box -- the uploaded one, after an update the refit one; the caller
+ *   puts it into rt_params.scene_aabb_min/max (the kernel's scene-box test reads the params).
+ * rt_last_update_timing: HIP-event time of the last update's kernels (ms). */
+int rt_refit_nodes(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx, rt_bvh_node* nodes, int32_t nn,
+                   const int32_t* refs, int32_t nref);
+int rt_update_vertices(rt_ctx* ctx, const rt_float4* verts, int32_t nv, const rt_float4* normals, int32_t nnorm);
+int rt_update_vertices_device(rt_ctx* ctx, const rt_float4* d_verts, int32_t nv, const rt_float4* d_normals,
+                              int32_t nnorm, void* stream);
+int rt_scene_bounds(rt_ctx* ctx, rt_float4* mn, rt_float4* mx);
+int rt_last_update_timing(rt_ctx* ctx, float* total_ms);
+
 /* Multi-GPU scene distribution ("ncclBroadcast of scene buffers at load").
  * The reference uploads one scene to its one device (RayTracer.cpp:942-984); here one
  * rank builds and uploads it, packs its device layouts into ONE contiguous device

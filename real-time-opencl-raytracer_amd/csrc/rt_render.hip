@@ -47,6 +47,8 @@
 #include <vector>
 
 #include "rt_abi.h"
+#include "rt_refit.h"
+#include "refit.hpp"
 
 #ifndef RTK_WF_WAVES
 #define RTK_WF_WAVES 7      // waves per SIMD the wavefront kernels are bounded to
@@ -1066,6 +1068,29 @@ struct rt_ctx {
     hipEvent_t gstart = nullptr;
     std::vector<FrameSlot*> last_group;   // the slots of the last grouped rt_render
     bool timing_valid = false;
+    // Animated geometry (rt_update_vertices): what a refittable scene keeps on the
+    // device besides its records -- per-triangle vertex / normal indices, the triangle of every
+    // reference record and the refit plan's level lists -- and the update's own buffers.
+    struct Refit {
+        bool have = false;
+        std::string why;                       // why the scene has no refit data
+        int32_t nv = 0, nnorm = 0;
+        uint32_t nref = 0, ntri = 0;
+        int32_t* d_idx = nullptr;
+        int32_t* d_normal_idx = nullptr;
+        int32_t* d_ref_tri = nullptr;
+        uint32_t* d_level_ids = nullptr;
+        uint32_t* d_level_begin = nullptr;
+        uint32_t* d_out = nullptr;             // rtrefit::DevArgs::out
+        float4* d_verts = nullptr;             // staging of the host form's arrays
+        float4* d_normals = nullptr;
+        std::vector<uint32_t> level_begin;     // host copy: heights + 1 entries
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // around the update's kernels; the caller's stream
+        bool timed = false;
+        uint32_t launches = 0;
+    } refit;
+    bool have_bounds = false;                  // rt_scene_bounds: the uploaded / refit root box
+    rt_float4 bounds_min{}, bounds_max{};
     std::string err;
 };
 
@@ -1127,7 +1152,7 @@ constexpr size_t kT0Slot = kRestartSlot + 1;   // the launch's start (RTK_LPT_BI
 constexpr size_t kCounters = kRestartSlot + 2;
 
 static int set_err(rt_ctx* c, const std::string& m, int code) {
-    if (c) c->err = m; else g_err = m;
+    if (c) c->err = m; else { g_err = m; rtrefit::clear_error(); }
     return code;
 }
 
@@ -1216,7 +1241,24 @@ static hipError_t alloc_records(rt_ctx* c, size_t n_wnodes4, size_t n_tris4) {
     return hipSuccess;
 }
 
+// a context without refit data (the events stay: rt_destroy)
+static void free_refit(rt_ctx* c, const char* why) {
+    rt_ctx::Refit& r = c->refit;
+    for (void* p : {(void*)r.d_idx, (void*)r.d_normal_idx, (void*)r.d_ref_tri, (void*)r.d_level_ids,
+                    (void*)r.d_level_begin, (void*)r.d_out, (void*)r.d_verts, (void*)r.d_normals})
+        if (p) (void)hipFree(p);
+    r.d_idx = r.d_normal_idx = r.d_ref_tri = nullptr;
+    r.d_level_ids = r.d_level_begin = r.d_out = nullptr;
+    r.d_verts = r.d_normals = nullptr;
+    r.level_begin.clear();
+    r.have = false;
+    r.timed = false;
+    r.why = why;
+}
+
 static void free_scene(rt_ctx* c) {
+    free_refit(c, "no scene uploaded");
+    c->have_bounds = false;
     if (c->split_records && c->d_tris) (void)hipFree(c->d_tris);
     if (c->d_wnodes) (void)hipFree(c->d_wnodes);   // (one block: inner records, then triangle records)
     if (c->d_shade) (void)hipFree(c->d_shade);
@@ -1474,7 +1516,11 @@ int rt_frame_checksum(const uint32_t* d_frame, uint64_t pixels, uint64_t* d_sum,
     return RT_OK;
 }
 
-const char* rt_last_error(rt_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
+// (without a context: the latest of the global message and rt_refit_nodes' own, csrc/host/refit.cpp)
+const char* rt_last_error(rt_ctx* ctx) {
+    if (ctx) return ctx->err.c_str();
+    return rtrefit::last_error().empty() ? g_err.c_str() : rtrefit::last_error().c_str();
+}
 
 int rt_create(int device, rt_ctx** out) {
     if (!out) return set_err(nullptr, "rt_create: out is NULL", RT_ERR_INVALID_ARG);
@@ -1521,6 +1567,8 @@ int rt_destroy(rt_ctx* c) {
         if (c->gstream[g]) (void)hipStreamDestroy(c->gstream[g]);
     }
     if (c->gstart) (void)hipEventDestroy(c->gstart);
+    for (hipEvent_t& e : c->refit.ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return RT_OK;
@@ -1695,6 +1743,126 @@ int rt_upload_scene(rt_ctx* c, const rt_float4* verts, int32_t nv, const int32_t
     c->clean = clean ? 1 : 0;
     c->have_scene = true;
     ++c->scene_gen;
+    c->bounds_min = nodes[0].min;
+    c->bounds_max = nodes[0].max;
+    c->have_bounds = true;
+    // refit data (rt_update_vertices): only a refittable scene gets it; any other renders as ever
+    rtrefit::Plan plan;
+    std::string why;
+    if (rtrefit::plan_build(nodes, nn, nref, inner_id.data(), plan, why) != RT_OK) {
+        c->refit.why = why;
+        return RT_OK;
+    }
+    if (plan.ids.size() != (size_t)n_inner) {   // (a refittable scene is clean: every inner node has a record)
+        c->refit.why = "refit: the plan does not cover the inner records";
+        return RT_OK;
+    }
+    rt_ctx::Refit& r = c->refit;
+    const uint32_t out0[8] = {(uint32_t)c->fast_div, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    float box[8];
+    std::memcpy(box, out0, sizeof box);
+    box[2] = nodes[0].min.x; box[3] = nodes[0].min.y; box[4] = nodes[0].min.z;
+    box[5] = nodes[0].max.x; box[6] = nodes[0].max.y; box[7] = nodes[0].max.z;
+    auto put = [&](auto*& d, const void* src, size_t bytes) {
+        hipError_t e = hipMalloc((void**)&d, std::max<size_t>(bytes, 16));
+        if (e == hipSuccess && bytes) e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
+        return e == hipSuccess;
+    };
+    if (!put(r.d_idx, idx, (size_t)nidx * 4) || !put(r.d_normal_idx, normal_idx, (size_t)nidx * 4) ||
+        !put(r.d_ref_tri, refs, (size_t)nref * 4) || !put(r.d_level_ids, plan.ids.data(), plan.ids.size() * 4) ||
+        !put(r.d_level_begin, plan.level_begin.data(), plan.level_begin.size() * 4) || !put(r.d_out, box, sizeof box)) {
+        (void)hipGetLastError();
+        free_refit(c, "refit: out of device memory for the refit data");
+        return RT_OK;
+    }
+    r.level_begin = plan.level_begin;
+    r.nv = nv;
+    r.nnorm = nnorm;
+    r.nref = (uint32_t)nref;
+    r.ntri = (uint32_t)ntri;
+    r.why.clear();
+    r.have = true;
+    return RT_OK;
+}
+
+// ---- animated geometry: vertex updates with an on-GPU refit ----
+// Both forms are synchronous, like rt_upload_scene: they wait for the frames in flight, run the
+// update on the context's stream, wait for it and read back the fast-quotient flag and the
+// root box.  scene_gen stays: the adaptive block order of a slightly moved scene is still a
+// good order, and pixels do not depend on it.
+static int update_vertices(rt_ctx* c, const char* who, const rt_float4* verts, int32_t nv, const rt_float4* normals,
+                           int32_t nnorm, bool on_device, void* stream) {
+    if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
+    if (!c->have_scene) return set_err(c, std::string(who) + ": no scene uploaded", RT_ERR_NO_SCENE);
+    rt_ctx::Refit& r = c->refit;
+    if (!r.have) return set_err(c, std::string(who) + ": the scene has no refit data (" + r.why + ")", RT_ERR_BAD_SCENE);
+    if (!verts || nv != r.nv || (normals && nnorm != r.nnorm))
+        return set_err(c, std::string(who) + ": vertices / normals must be the upload's counts (" + std::to_string(r.nv) +
+                              ", " + std::to_string(r.nnorm) + ")", RT_ERR_INVALID_ARG);
+    HIPC(c, hipSetDevice(c->device));
+    for (hipEvent_t& e : r.ev)
+        if (!e) HIPC(c, hipEventCreate(&e));
+    for (auto& f : c->slots)
+        if (f.idle) HIPC(c, hipEventSynchronize(f.idle));   // frames in flight still read the old records
+    const float4* d_verts = (const float4*)verts;
+    const float4* d_normals = (const float4*)normals;
+    if (on_device) {   // the caller's stream may still be producing d_verts
+        HIPC(c, hipEventRecord(r.ev[2], (hipStream_t)stream));
+        HIPC(c, hipStreamWaitEvent(c->stream, r.ev[2], 0));
+    } else {
+        if (!r.d_verts) HIPC(c, hipMalloc((void**)&r.d_verts, (size_t)r.nv * sizeof(float4)));
+        HIPC(c, hipMemcpyAsync(r.d_verts, verts, (size_t)r.nv * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        d_verts = r.d_verts;
+        if (normals) {
+            if (!r.d_normals) HIPC(c, hipMalloc((void**)&r.d_normals, (size_t)r.nnorm * sizeof(float4)));
+            HIPC(c, hipMemcpyAsync(r.d_normals, normals, (size_t)r.nnorm * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+            d_normals = r.d_normals;
+        }
+    }
+    rtrefit::DevArgs a{};
+    a.wnodes = c->d_wnodes; a.tris = c->d_tris; a.shade = c->d_shade; a.leaf_table = c->d_leaf;
+    a.verts = d_verts; a.normals = d_normals;
+    a.idx = r.d_idx; a.normal_idx = r.d_normal_idx; a.ref_tri = r.d_ref_tri;
+    a.level_ids = r.d_level_ids; a.level_begin = r.d_level_begin; a.out = r.d_out;
+    a.nref = r.nref; a.ntri = r.ntri; a.n_inner = c->n_inner; a.root = c->root;
+    HIPC(c, hipEventRecord(r.ev[0], c->stream));
+    HIPC(c, rtrefit::launch(a, r.level_begin.data(), (uint32_t)r.level_begin.size() - 1u, c->stream, &r.launches));
+    HIPC(c, hipEventRecord(r.ev[1], c->stream));
+    uint32_t out[8] = {};
+    HIPC(c, hipMemcpyAsync(out, r.d_out, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, wait_stream(c->stream));
+    r.timed = true;
+    c->fast_div = out[0] ? 1 : 0;
+    float box[6];
+    std::memcpy(box, out + 2, sizeof box);
+    c->bounds_min.x = box[0]; c->bounds_min.y = box[1]; c->bounds_min.z = box[2];
+    c->bounds_max.x = box[3]; c->bounds_max.y = box[4]; c->bounds_max.z = box[5];
+    return RT_OK;
+}
+
+int rt_update_vertices(rt_ctx* c, const rt_float4* verts, int32_t nv, const rt_float4* normals, int32_t nnorm) {
+    return update_vertices(c, "rt_update_vertices", verts, nv, normals, nnorm, false, nullptr);
+}
+
+int rt_update_vertices_device(rt_ctx* c, const rt_float4* d_verts, int32_t nv, const rt_float4* d_normals, int32_t nnorm,
+                              void* stream) {
+    return update_vertices(c, "rt_update_vertices_device", d_verts, nv, d_normals, nnorm, true, stream);
+}
+
+int rt_scene_bounds(rt_ctx* c, rt_float4* mn, rt_float4* mx) {
+    if (!c || !mn || !mx) return set_err(c, "rt_scene_bounds: invalid argument", RT_ERR_INVALID_ARG);
+    if (!c->have_scene) return set_err(c, "rt_scene_bounds: no scene uploaded", RT_ERR_NO_SCENE);
+    if (!c->have_bounds)
+        return set_err(c, "rt_scene_bounds: the scene came from a scene image, which carries no root box", RT_ERR_BAD_SCENE);
+    *mn = c->bounds_min;
+    *mx = c->bounds_max;
+    return RT_OK;
+}
+
+int rt_last_update_timing(rt_ctx* c, float* total_ms) {
+    if (!c || !total_ms) return set_err(c, "rt_last_update_timing: invalid argument", RT_ERR_INVALID_ARG);
+    if (!c->refit.timed) return set_err(c, "rt_last_update_timing: no update since the upload", RT_ERR_INVALID_ARG);
+    HIPC(c, hipEventElapsedTime(total_ms, c->refit.ev[0], c->refit.ev[1]));
     return RT_OK;
 }
 
@@ -1776,6 +1944,7 @@ int rt_scene_image_load(rt_ctx* c, const void* d_image, uint64_t bytes, void* st
     c->n_inner = h.n_inner;
     c->fast_div = h.fast_div;
     c->clean = h.clean;
+    c->refit.why = "the scene came from rt_scene_image_load; upload it with rt_upload_scene to update it";
     c->have_scene = true;
     ++c->scene_gen;
     return RT_OK;
@@ -2512,6 +2681,10 @@ int rt_scene_copy(rt_ctx* dst, rt_ctx* src) {
     dst->n_inner = src->n_inner;
     dst->fast_div = src->fast_div;
     dst->clean = src->clean;
+    dst->refit.why = "the scene came from rt_scene_copy; upload it with rt_upload_scene to update it";
+    dst->have_bounds = src->have_bounds;
+    dst->bounds_min = src->bounds_min;
+    dst->bounds_max = src->bounds_max;
     dst->have_scene = true;
     ++dst->scene_gen;
     return RT_OK;

@@ -9,12 +9,14 @@
 // (a list; a device may repeat) every frame goes to rt_render_tiled over one context per
 // entry instead: the scene is uploaded once and copied to the others (rt_scene_copy).  With
 // --batch K the orbit's next K cameras go to ONE rt_render_batch call (the throughput mode: K frames
-// in one launch, read back together).
+// in one launch, read back together).  With --animate the mesh deforms: before frame f the vertices
+// become base * (1 + f / 64) through rt_update_vertices (the records and the BVH boxes are refitted on
+// the GPU) and the frame's scene box is rt_scene_bounds'.
 //
 //   rt_frameloop [--dae F | --obj F | --scene cornell|knot|heightfield] [--bvh-cache F]
 //                [--width W] [--height H] [--depth D] [--frames N] [--drag DX DY]
 //                [--ppm-dir DIR] [--ppm-every K] [--device I] [--flags F] [--gpus N | --devices a,b,...]
-//                [--batch K]
+//                [--batch K] [--animate]
 //
 // Prints "N.N fps" lines and a final JSON summary.
 #include <algorithm>
@@ -37,6 +39,7 @@ struct Args {
     uint32_t flags = 0;
     float dx = 4.0f, dy = 0.0f;
     std::vector<int> devices;   // rt_render_tiled over these (empty: rt_render on --device)
+    bool animate = false;       // rt_update_vertices before every frame
 };
 
 int usage() {
@@ -44,7 +47,7 @@ int usage() {
                  "usage: rt_frameloop [--dae F | --obj F | --scene cornell|knot|heightfield] [--bvh-cache F]\n"
                  "                    [--width W] [--height H] [--depth D] [--frames N] [--drag DX DY]\n"
                  "                    [--ppm-dir DIR] [--ppm-every K] [--device I] [--flags F]\n"
-                 "                    [--gpus N | --devices a,b,...] [--batch K]\n");
+                 "                    [--gpus N | --devices a,b,...] [--batch K] [--animate]\n");
     return 2;
 }
 
@@ -66,6 +69,7 @@ bool parse(int argc, char** argv, Args& a) {
         else if (k == "--device" && need(1)) a.device = std::atoi(argv[++i]);
         else if (k == "--flags" && need(1)) a.flags = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
         else if (k == "--batch" && need(1)) a.batch = std::atoi(argv[++i]);
+        else if (k == "--animate") a.animate = true;
         else if (k == "--gpus" && need(1)) {
             const int n = std::atoi(argv[++i]);
             if (n < 1 || n > 64) return false;
@@ -85,7 +89,8 @@ bool parse(int argc, char** argv, Args& a) {
         } else return false;
     }
     return a.w > 0 && a.h > 0 && a.frames > 0 && a.depth >= 0 && a.depth <= RT_MAX_DEPTH && a.batch >= 1 &&
-           a.batch <= RT_MAX_BATCH && (a.batch == 1 || a.devices.size() <= 1);
+           a.batch <= RT_MAX_BATCH && (a.batch == 1 || a.devices.size() <= 1) &&
+           (!a.animate || (a.batch == 1 && a.devices.size() <= 1));   // the update is one context's
 }
 
 // Packed pixels are b<<16 | g<<8 | r (volumeRender.cl:186-195); row 0 is the first image row.
@@ -165,13 +170,32 @@ int main(int argc, char** argv) {
     std::vector<uint32_t> px(npx * (size_t)a.batch), one;
     std::vector<rt_params> cams((size_t)a.batch);
     int frames_in_second = 0, total = 0;
-    double kernel_ms_sum = 0.0;
+    double kernel_ms_sum = 0.0, update_ms_sum = 0.0;
+    std::vector<rt_float4> moved(a.animate ? (size_t)mv.num_vertices : 0);
     auto t0 = clk::now(), tsec = t0;
     for (int f0 = 0; f0 < a.frames; f0 += a.batch) {
         const int k = std::min(a.batch, a.frames - f0);   // this call's frames f0 .. f0 + k - 1
         for (int i = 0; i < k; ++i) {
             if (f0 + i > 0) rt_camera_add_rotate(cam, a.dx * 0.25f / 100.0f, a.dy * 0.25f / 100.0f);  // motion()
             rt_camera_frame_params(cam, mesh, a.w, a.h, nullptr, nullptr, &cams[(size_t)i]);     // updateCamera()
+        }
+        if (a.animate) {   // frame f0's mesh: one float multiply per coordinate
+            const float s = 1.0f + (float)f0 * 0.015625f;
+            for (int32_t v = 0; v < mv.num_vertices; ++v) {
+                const rt_float4 b = mv.vertices[v];
+                moved[(size_t)v] = rt_float4{b.x * s, b.y * s, b.z * s, b.w};
+            }
+            rt_float4 mn, mx;
+            float ums = 0.0f;
+            if ((rc = rt_update_vertices(ctx, moved.data(), mv.num_vertices, nullptr, 0)) != RT_OK ||
+                (rc = rt_scene_bounds(ctx, &mn, &mx)) != RT_OK || (rc = rt_last_update_timing(ctx, &ums)) != RT_OK) {
+                std::fprintf(stderr, "frame %d: %s\n", f0, rt_last_error(ctx));
+                return 1;
+            }
+            update_ms_sum += ums;
+            rt_params& p = cams[0];   // the kernel's scene-box test reads the params' box
+            p.scene_aabb_min.x = mn.x; p.scene_aabb_min.y = mn.y; p.scene_aabb_min.z = mn.z;
+            p.scene_aabb_max.x = mx.x; p.scene_aabb_max.y = mx.y; p.scene_aabb_max.z = mx.z;
         }
         if (a.batch > 1) {
             rc = rt_render_batch(ctx, a.w, a.h, a.depth, a.flags, cams.data(), k, px.data());
@@ -206,11 +230,13 @@ int main(int argc, char** argv) {
         }
     }
     const double wall = std::chrono::duration<double>(clk::now() - t0).count();
+    char anim[64] = "";   // --animate only: the JSON line is otherwise as ever
+    if (a.animate) std::snprintf(anim, sizeof anim, ", \"update_ms_mean\": %.4f", update_ms_sum / total);
     std::printf("{\"frames\": %d, \"width\": %u, \"height\": %u, \"depth\": %d, \"fps\": %.2f, \"ms_per_frame\": %.4f, "
                 "\"kernel_ms_per_frame\": %.4f, \"triangles\": %d, \"bvh_nodes\": %d, \"bvh_cached\": %s, "
-                "\"bvh_seconds\": %.3f, \"contexts\": %d, \"frames_per_call\": %d}\n",
+                "\"bvh_seconds\": %.3f, \"contexts\": %d, \"frames_per_call\": %d%s}\n",
                 total, a.w, a.h, a.depth, total / wall, 1e3 * wall / total, kernel_ms_sum / total,
-                mv.num_indices / 3, bv.num_nodes, cached ? "true" : "false", bvh_s, nctx, a.batch);
+                mv.num_indices / 3, bv.num_nodes, cached ? "true" : "false", bvh_s, nctx, a.batch, anim);
     rt_camera_destroy(cam);
     for (rt_ctx* c : ctxs) rt_destroy(c);
     rt_bvh_destroy(bvh);

@@ -91,7 +91,9 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_frame_sync_status", "rt_frame_checksum", "rt_shared_alloc", "rt_shared_free", "rt_copy_device",
                "rt_scene_image_size", "rt_scene_image_pack",
                "rt_scene_image_load", "rt_fetch_counts", "rt_gather_peak", "rt_chase_peak", "rt_chase_latency", "rt_wave_timeline", "rt_last_timing", "rt_timing_average", "rt_last_deferred", "rt_overflow_count", "rt_destroy", "rt_last_error",
-               "rt_abi_version"]
+               "rt_abi_version",
+               "rt_refit_nodes", "rt_update_vertices", "rt_update_vertices_device", "rt_scene_bounds",
+               "rt_last_update_timing"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
                 "rt_mesh_load_dae", "rt_mesh_save_dae",
                 "rt_mesh_gen_cornell", "rt_mesh_gen_torus_knot", "rt_mesh_gen_heightfield", "rt_mesh_gen_random",
@@ -170,6 +172,11 @@ def lib() -> C.CDLL:
             "rt_destroy": (C.c_int, [vp]),
             "rt_last_error": (C.c_char_p, [vp]),
             "rt_abi_version": (C.c_int, []),
+            "rt_refit_nodes": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32]),
+            "rt_update_vertices": (C.c_int, [vp, vp, i32, vp, i32]),
+            "rt_update_vertices_device": (C.c_int, [vp, vp, i32, vp, i32, vp]),
+            "rt_scene_bounds": (C.c_int, [vp, C.POINTER(rt_float4), C.POINTER(rt_float4)]),
+            "rt_last_update_timing": (C.c_int, [vp, C.POINTER(f32)]),
             "rt_mesh_create": (vp, []),
             "rt_mesh_destroy": (None, [vp]),
             "rt_mesh_view_get": (C.c_int, [vp, C.POINTER(rt_mesh_view)]),
@@ -277,6 +284,19 @@ class Scene:
         m = mesh.arrays()
         return Scene(m["vertices"], m["indices"], bvh.nodes, bvh.tri_indices, m["normals"],
                      m["normals_indices"], m["materials"], m["tri_to_material"], m["scene_min"], m["scene_max"])
+
+
+def refit_nodes(scene: Scene, vertices) -> np.ndarray:
+    """rt_refit_nodes: the scene's BVH nodes refitted on the CPU to `vertices` (float32 (nv, 4)) --
+    a new (nn, 12) array; the scene is not modified.  What Renderer.update_vertices computes on the
+    GPU: uploading (vertices, these nodes) gives the same device records."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 4)
+    nodes = np.array(scene.nodes, dtype=np.float32, order="C", copy=True).reshape(-1, 12)
+    idx = np.ascontiguousarray(scene.indices, dtype=np.int32)
+    refs = np.ascontiguousarray(scene.tri_indices, dtype=np.int32)
+    _check(lib().rt_refit_nodes(_ptr(v), v.shape[0], _ptr(idx), idx.size, _ptr(nodes), nodes.shape[0], _ptr(refs),
+                                refs.size))
+    return nodes
 
 
 class Mesh:
@@ -463,6 +483,36 @@ class Renderer:
             _ptr(s.nodes), s.nodes.shape[0], _ptr(s.tri_indices), s.tri_indices.size,
             _ptr(s.normals), s.normals.shape[0], _ptr(s.normals_indices), _ptr(s.materials), s.materials.shape[0],
             _ptr(s.tri_to_material)), self._h)
+
+    def update_vertices(self, vertices, normals=None) -> None:
+        """rt_update_vertices: new vertices (and normals) for the uploaded scene; the triangle,
+        shading and inner records are rewritten on the GPU (BVH refit).  `vertices`: float32
+        (nv, 4), or a (device pointer, stream) pair for rt_update_vertices_device (`normals` is
+        then a device pointer or None); the counts must be the upload's."""
+        s = getattr(self, "_scene_keepalive", None)
+        nv = s.vertices.shape[0] if s is not None else 0
+        nn = s.normals.shape[0] if s is not None else 0
+        if isinstance(vertices, tuple):
+            d_verts, stream = vertices
+            _check(lib().rt_update_vertices_device(self._h, C.c_void_p(d_verts), nv, C.c_void_p(normals or None), nn,
+                                                   C.c_void_p(stream or None)), self._h)
+            return
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 4)
+        n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 4)
+        _check(lib().rt_update_vertices(self._h, _ptr(v), v.shape[0], _ptr(n), 0 if n is None else n.shape[0]), self._h)
+
+    def scene_bounds(self):
+        """rt_scene_bounds: (min, max) float32[3] of the root box, the refit one after an update
+        (goes into the params' scene_aabb_min/max)."""
+        mn, mx = rt_float4(), rt_float4()
+        _check(lib().rt_scene_bounds(self._h, C.byref(mn), C.byref(mx)), self._h)
+        return (np.array([mn.x, mn.y, mn.z], np.float32), np.array([mx.x, mx.y, mx.z], np.float32))
+
+    def last_update_ms(self) -> float:
+        """rt_last_update_timing: kernel time of the last update_vertices (ms)."""
+        ms = C.c_float()
+        _check(lib().rt_last_update_timing(self._h, C.byref(ms)), self._h)
+        return ms.value
 
     def scene_image_size(self) -> int:
         """Bytes of this ctx's scene image (rt_scene_image_size)."""
