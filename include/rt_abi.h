@@ -177,6 +177,36 @@ int rt_update_vertices_device(rt_ctx* ctx, const rt_float4* d_verts, int32_t nv,
 int rt_scene_bounds(rt_ctx* ctx, rt_float4* mn, rt_float4* mx);
 int rt_last_update_timing(rt_ctx* ctx, float* total_ms);
 
+/* On-GPU BVH build.  The reference builds its BVH on the host (SplitBVHBuilder::run,
+ * SplitBVHBuilder.cpp:41-476, flattened by BVH_Cuda::build_from_bvh2, BVH_Cuda.h:87-137) before
+ * initRayTrace uploads it; a new or heavily deformed mesh waits for that build.  Here a linear BVH
+ * is built by the GPU into the same two arrays -- BVH_Node_[] and tri_indices[] -- which
+ * rt_upload_scene, rt_refit_nodes and the BVH cache take unchanged: Morton keys of the triangle
+ * centroids (13 bits per axis, the triangle index below them), a device radix sort, the binary
+ * radix tree over the sorted keys (Karras 2012), subtrees of at most max_leaf (1..8) triangles
+ * collapsed into leaves, boxes fitted bottom-up with rt_refit_nodes' semantics.  Every triangle is
+ * kept (nref = nidx / 3, written to refs[0 .. nidx/3)); the root is node 0; the node order is the
+ * builder's own (kept nodes, then leaves), not pre-order.  rt_bvh_build_lbvh (rt_host.h) builds
+ * the same bytes on the host.
+ *
+ * rt_build_bvh: host arrays in and out.  rt_build_bvh_device: device arrays in and out, the inputs
+ *   produced on `stream` (NULL = the null stream); d_verts and d_nodes 16-byte aligned.  Both are
+ *   synchronous: they run on the context's stream and return when nodes / refs are complete and
+ *   *num_nodes is set.  The uploaded scene, if any, is neither read nor changed.
+ * n = nidx / 3 triangles need node_cap >= 2n - 1 and ref_cap >= n.  RT_ERR_INVALID_ARG, before any
+ *   GPU work: smaller capacities, max_leaf outside 1..8, nidx % 3 != 0, n outside [1, 2^25], a NULL
+ *   pointer.  RT_ERR_BAD_SCENE: an index outside [0, nv) -- found on the host by rt_build_bvh, by
+ *   the first kernel for device arrays (no kernel reads a vertex through such an index, and nothing
+ *   after that kernel runs).  The context stays usable after either.
+ * rt_last_build_timing: HIP-event time (ms) from the first to the last kernel of the context's
+ *   last successful build, the two short host reads in between (index flag, depth counts) included. */
+int rt_build_bvh(rt_ctx* ctx, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx, int32_t max_leaf,
+                 rt_bvh_node* nodes, int32_t node_cap, int32_t* refs, int32_t ref_cap, int32_t* num_nodes);
+int rt_build_bvh_device(rt_ctx* ctx, const rt_float4* d_verts, int32_t nv, const int32_t* d_idx, int32_t nidx,
+                        int32_t max_leaf, rt_bvh_node* d_nodes, int32_t node_cap, int32_t* d_refs, int32_t ref_cap,
+                        int32_t* num_nodes, void* stream);
+int rt_last_build_timing(rt_ctx* ctx, float* total_ms);
+
 /* Multi-GPU scene distribution ("ncclBroadcast of scene buffers at load").
  * The reference uploads one scene to its one device (RayTracer.cpp:942-984); here one
  * rank builds and uploads it, packs its device layouts into ONE contiguous device

@@ -85,6 +85,13 @@ int rt_bvh_build(const rt_mesh* m, int32_t max_leaf, int32_t num_threads, rt_bvh
  * parallel (num_threads <= 0: all cores); replaces the reference's
  * single-threaded 317 s build of a 1M-triangle mesh. */
 int rt_bvh_build_sbvh(const rt_mesh* m, int32_t num_threads, rt_bvh** out);
+/* The linear BVH of DESIGN.md 15 on the host: Morton keys of the triangle centroids, the binary
+ * radix tree over the sorted keys, subtrees of at most max_leaf (1..8) triangles collapsed into
+ * leaves, boxes fitted bottom-up.  Byte for byte what rt_build_bvh (rt_abi.h) builds on the GPU;
+ * same BVH_Node_ / tri_indices layout as the other builders (BVH_Cuda.h:87-137), root = node 0,
+ * but the node order is its own (kept nodes, then leaves), not pre-order.  Every triangle is
+ * kept.  RT_ERR_INVALID_ARG: max_leaf outside 1..8, no triangle or more than 2^25. */
+int rt_bvh_build_lbvh(const rt_mesh* m, int32_t max_leaf, rt_bvh** out);
 int rt_bvh_view_get(const rt_bvh* b, rt_bvh_view* out);
 void rt_bvh_destroy(rt_bvh* b);
 /* BVH cache file (nodes + refs + mesh hash), SURVEY.md 5 "checkpoint". */

@@ -6,9 +6,8 @@
 
 #include "rt_host.h"
 #include "scene.hpp"
+#include "rt_handles.hpp"
 
-struct rt_mesh { rtamd::Mesh m; };
-struct rt_bvh { rtamd::Bvh b; };
 struct rt_camera { rtamd::Camera c; explicit rt_camera(float r) : c(r) {} };
 
 extern "C" {

@@ -54,6 +54,10 @@ void append_grid(Mesh& dst, const Mesh& src, int gx, int gz, float dx, float dz,
 void build_bvh(const Mesh& m, int max_leaf, int num_threads, Bvh& out);
 // The reference SplitBVHBuilder (SplitBVHBuilder.cpp:41-476) + BVH_Cuda::build_from_bvh2, same bytes.
 void build_sbvh(const Mesh& m, int num_threads, Bvh& out);
+// The LBVH of DESIGN.md 15 (lbvh_builder.cpp): the host twin of rt_build_bvh, same bytes.  max_leaf 1..8,
+// 1 <= nidx / 3 <= 2^25; RT_ERR_INVALID_ARG / RT_ERR_BAD_SCENE (an index out of range) with `err` set.
+int build_lbvh(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx, int max_leaf, Bvh& out,
+               std::string& err);
 
 // Camera (Camera.cpp:6-68): orbit around the origin; angles accumulate in float as the reference's do.
 struct Camera {

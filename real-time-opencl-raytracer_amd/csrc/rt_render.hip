@@ -49,6 +49,8 @@
 #include "rt_abi.h"
 #include "rt_refit.h"
 #include "refit.hpp"
+#include "rt_lbvh.h"
+#include "lbvh_core.hpp"
 
 #ifndef RTK_WF_WAVES
 #define RTK_WF_WAVES 7      // waves per SIMD the wavefront kernels are bounded to
@@ -1089,7 +1091,8 @@ struct rt_ctx {
         bool timed = false;
         uint32_t launches = 0;
     } refit;
-    bool have_bounds = false;                  // rt_scene_bounds: the uploaded / refit root box
+    rtlbvh::Scratch lbvh;                      // rt_build_bvh's buffers; no part of the scene
+    bool have_bounds = false;                 // rt_scene_bounds: the uploaded / refit root box
     rt_float4 bounds_min{}, bounds_max{};
     std::string err;
 };
@@ -1569,6 +1572,7 @@ int rt_destroy(rt_ctx* c) {
     if (c->gstart) (void)hipEventDestroy(c->gstart);
     for (hipEvent_t& e : c->refit.ev)
         if (e) (void)hipEventDestroy(e);
+    rtlbvh::release(c->lbvh);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return RT_OK;
@@ -1863,6 +1867,94 @@ int rt_last_update_timing(rt_ctx* c, float* total_ms) {
     if (!c || !total_ms) return set_err(c, "rt_last_update_timing: invalid argument", RT_ERR_INVALID_ARG);
     if (!c->refit.timed) return set_err(c, "rt_last_update_timing: no update since the upload", RT_ERR_INVALID_ARG);
     HIPC(c, hipEventElapsedTime(total_ms, c->refit.ev[0], c->refit.ev[1]));
+    return RT_OK;
+}
+
+// ---- on-GPU LBVH build ----
+// Both forms are synchronous.  They run on the context's stream with the context's own scratch
+// and touch nothing of the uploaded scene: frames in flight on other streams are not waited for.
+static int build_bvh(rt_ctx* c, const char* who, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx,
+                     int32_t max_leaf, rt_bvh_node* nodes, int32_t node_cap, int32_t* refs, int32_t ref_cap,
+                     int32_t* num_nodes, bool on_device, void* stream) {
+    if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
+    if (!verts || nv <= 0 || !idx || !nodes || !refs || !num_nodes)
+        return set_err(c, std::string(who) + ": missing array", RT_ERR_INVALID_ARG);
+    if (max_leaf < 1 || max_leaf > 8) return set_err(c, std::string(who) + ": max_leaf must be 1 .. 8", RT_ERR_INVALID_ARG);
+    if (nidx <= 0 || nidx % 3 != 0 || nidx / 3 > lbvh::kMaxTris)
+        return set_err(c, std::string(who) + ": needs 1 .. 2^25 triangles, 3 indices each", RT_ERR_INVALID_ARG);
+    const int32_t n = nidx / 3;
+    if ((int64_t)node_cap < 2 * (int64_t)n - 1 || ref_cap < n)
+        return set_err(c, std::string(who) + ": needs room for 2n - 1 nodes and n references", RT_ERR_INVALID_ARG);
+    rtlbvh::Scratch& S = c->lbvh;
+    if (on_device) {
+        if (((uintptr_t)verts | (uintptr_t)nodes) & 15u)
+            return set_err(c, std::string(who) + ": d_verts and d_nodes must be 16-byte aligned", RT_ERR_INVALID_ARG);
+    } else {
+        for (int32_t i = 0; i < nidx; ++i)
+            if (idx[i] < 0 || idx[i] >= nv) return set_err(c, "mesh_indices out of range", RT_ERR_BAD_SCENE);
+    }
+    HIPC(c, hipSetDevice(c->device));
+    for (hipEvent_t& e : S.ev)
+        if (!e) HIPC(c, hipEventCreate(&e));
+    S.timed = false;
+    const float4* d_verts = (const float4*)verts;
+    const int32_t* d_idx = idx;
+    float4* d_nodes = (float4*)nodes;
+    int32_t* d_refs = refs;
+    if (on_device) {   // the caller's stream may still be producing the inputs
+        HIPC(c, hipEventRecord(S.ev[2], (hipStream_t)stream));
+        HIPC(c, hipStreamWaitEvent(c->stream, S.ev[2], 0));
+    } else {
+        if (rtlbvh::reserve(S.verts, (size_t)nv * sizeof(float4)) != hipSuccess ||
+            rtlbvh::reserve(S.idx, (size_t)nidx * 4) != hipSuccess ||
+            rtlbvh::reserve(S.nodes, (size_t)(2 * (int64_t)n - 1) * sizeof(rt_bvh_node)) != hipSuccess ||
+            rtlbvh::reserve(S.refs, (size_t)n * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(c, std::string(who) + ": out of device memory", RT_ERR_OUT_OF_MEMORY);
+        }
+        HIPC(c, hipMemcpyAsync(S.verts.p, verts, (size_t)nv * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        HIPC(c, hipMemcpyAsync(S.idx.p, idx, (size_t)nidx * 4, hipMemcpyHostToDevice, c->stream));
+        d_verts = (const float4*)S.verts.p;
+        d_idx = (const int32_t*)S.idx.p;
+        d_nodes = (float4*)S.nodes.p;
+        d_refs = (int32_t*)S.refs.p;
+    }
+    HIPC(c, hipEventRecord(S.ev[0], c->stream));
+    std::string err;
+    int32_t nn = 0;
+    const int rc = rtlbvh::build(S, c->stream, d_verts, nv, d_idx, n, max_leaf, d_nodes, 2 * n - 1, d_refs, &nn, err);
+    if (rc != RT_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return set_err(c, rc == RT_ERR_BAD_SCENE ? err : std::string(who) + ": " + err, rc);
+    }
+    HIPC(c, hipEventRecord(S.ev[1], c->stream));
+    if (!on_device) {
+        HIPC(c, hipMemcpyAsync(nodes, d_nodes, (size_t)nn * sizeof(rt_bvh_node), hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipMemcpyAsync(refs, d_refs, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    S.timed = true;
+    *num_nodes = nn;
+    return RT_OK;
+}
+
+int rt_build_bvh(rt_ctx* c, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx, int32_t max_leaf,
+                 rt_bvh_node* nodes, int32_t node_cap, int32_t* refs, int32_t ref_cap, int32_t* num_nodes) {
+    return build_bvh(c, "rt_build_bvh", verts, nv, idx, nidx, max_leaf, nodes, node_cap, refs, ref_cap, num_nodes, false,
+                     nullptr);
+}
+
+int rt_build_bvh_device(rt_ctx* c, const rt_float4* d_verts, int32_t nv, const int32_t* d_idx, int32_t nidx,
+                        int32_t max_leaf, rt_bvh_node* d_nodes, int32_t node_cap, int32_t* d_refs, int32_t ref_cap,
+                        int32_t* num_nodes, void* stream) {
+    return build_bvh(c, "rt_build_bvh_device", d_verts, nv, d_idx, nidx, max_leaf, d_nodes, node_cap, d_refs, ref_cap,
+                     num_nodes, true, stream);
+}
+
+int rt_last_build_timing(rt_ctx* c, float* total_ms) {
+    if (!c || !total_ms) return set_err(c, "rt_last_build_timing: invalid argument", RT_ERR_INVALID_ARG);
+    if (!c->lbvh.timed) return set_err(c, "rt_last_build_timing: no successful build on this context", RT_ERR_INVALID_ARG);
+    HIPC(c, hipEventElapsedTime(total_ms, c->lbvh.ev[0], c->lbvh.ev[1]));
     return RT_OK;
 }
 

@@ -11,12 +11,14 @@
 // --batch K the orbit's next K cameras go to ONE rt_render_batch call (the throughput mode: K frames
 // in one launch, read back together).  With --animate the mesh deforms: before frame f the vertices
 // become base * (1 + f / 64) through rt_update_vertices (the records and the BVH boxes are refitted on
-// the GPU) and the frame's scene box is rt_scene_bounds'.
+// the GPU) and the frame's scene box is rt_scene_bounds'.  With --gpu-build the scene's BVH is
+// built on the GPU (rt_build_bvh, leaves of at most --max-leaf triangles, default 2) instead of by the
+// host builder, and the summary reports build_ms, the build's kernel time.
 //
 //   rt_frameloop [--dae F | --obj F | --scene cornell|knot|heightfield] [--bvh-cache F]
 //                [--width W] [--height H] [--depth D] [--frames N] [--drag DX DY]
 //                [--ppm-dir DIR] [--ppm-every K] [--device I] [--flags F] [--gpus N | --devices a,b,...]
-//                [--batch K] [--animate]
+//                [--batch K] [--animate] [--gpu-build [--max-leaf N]]
 //
 // Prints "N.N fps" lines and a final JSON summary.
 #include <algorithm>
@@ -40,6 +42,8 @@ struct Args {
     float dx = 4.0f, dy = 0.0f;
     std::vector<int> devices;   // rt_render_tiled over these (empty: rt_render on --device)
     bool animate = false;       // rt_update_vertices before every frame
+    bool gpu_build = false;     // rt_build_bvh instead of the host builder
+    int max_leaf = 2;
 };
 
 int usage() {
@@ -47,7 +51,8 @@ int usage() {
                  "usage: rt_frameloop [--dae F | --obj F | --scene cornell|knot|heightfield] [--bvh-cache F]\n"
                  "                    [--width W] [--height H] [--depth D] [--frames N] [--drag DX DY]\n"
                  "                    [--ppm-dir DIR] [--ppm-every K] [--device I] [--flags F]\n"
-                 "                    [--gpus N | --devices a,b,...] [--batch K] [--animate]\n");
+                 "                    [--gpus N | --devices a,b,...] [--batch K] [--animate]\n"
+                 "                    [--gpu-build [--max-leaf N]]\n");
     return 2;
 }
 
@@ -70,6 +75,8 @@ bool parse(int argc, char** argv, Args& a) {
         else if (k == "--flags" && need(1)) a.flags = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
         else if (k == "--batch" && need(1)) a.batch = std::atoi(argv[++i]);
         else if (k == "--animate") a.animate = true;
+        else if (k == "--gpu-build") a.gpu_build = true;
+        else if (k == "--max-leaf" && need(1)) a.max_leaf = std::atoi(argv[++i]);
         else if (k == "--gpus" && need(1)) {
             const int n = std::atoi(argv[++i]);
             if (n < 1 || n > 64) return false;
@@ -90,7 +97,8 @@ bool parse(int argc, char** argv, Args& a) {
     }
     return a.w > 0 && a.h > 0 && a.frames > 0 && a.depth >= 0 && a.depth <= RT_MAX_DEPTH && a.batch >= 1 &&
            a.batch <= RT_MAX_BATCH && (a.batch == 1 || a.devices.size() <= 1) &&
-           (!a.animate || (a.batch == 1 && a.devices.size() <= 1));   // the update is one context's
+           (!a.animate || (a.batch == 1 && a.devices.size() <= 1)) &&   // the update is one context's
+           a.max_leaf >= 1 && a.max_leaf <= 8;
 }
 
 // Packed pixels are b<<16 | g<<8 | r (volumeRender.cl:186-195); row 0 is the first image row.
@@ -132,17 +140,17 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     rt_bvh* bvh = nullptr;
     bool cached = false;
-    if (!a.bvh_cache.empty() && rt_bvh_load(mesh, a.bvh_cache.c_str(), &bvh) == RT_OK) cached = true;
-    if (!bvh) {
+    if (!a.gpu_build && !a.bvh_cache.empty() && rt_bvh_load(mesh, a.bvh_cache.c_str(), &bvh) == RT_OK) cached = true;
+    if (!bvh && !a.gpu_build) {
         if ((rc = rt_bvh_build_sbvh(mesh, 0, &bvh)) != RT_OK) { std::fprintf(stderr, "bvh build failed\n"); return 1; }
         if (!a.bvh_cache.empty()) rt_bvh_save(bvh, mesh, a.bvh_cache.c_str());
     }
-    const double bvh_s = std::chrono::duration<double>(clk::now() - tb).count();
+    double bvh_s = std::chrono::duration<double>(clk::now() - tb).count();
 
     rt_mesh_view mv;
-    rt_bvh_view bv;
+    rt_bvh_view bv{};
     rt_mesh_view_get(mesh, &mv);
-    rt_bvh_view_get(bvh, &bv);
+    if (bvh) rt_bvh_view_get(bvh, &bv);
     // one context per GPU entry (a single one on --device without --gpus / --devices)
     if (a.devices.empty()) a.devices.push_back(a.device);
     std::vector<rt_ctx*> ctxs(a.devices.size(), nullptr);
@@ -152,6 +160,27 @@ int main(int argc, char** argv) {
             return 1;
         }
     rt_ctx* ctx = ctxs[0];
+    std::vector<rt_bvh_node> gpu_nodes;
+    std::vector<int32_t> gpu_refs;
+    float build_ms = 0.0f;
+    if (a.gpu_build) {   // the BVH from the GPU: the same two arrays, into host memory
+        const auto tg = clk::now();
+        const int32_t ntri = mv.num_indices / 3;
+        gpu_nodes.resize((size_t)std::max(2 * ntri - 1, 1));
+        gpu_refs.resize((size_t)std::max(ntri, 1));
+        int32_t nn = 0;
+        rc = rt_build_bvh(ctx, mv.vertices, mv.num_vertices, mv.indices, mv.num_indices, a.max_leaf, gpu_nodes.data(),
+                          (int32_t)gpu_nodes.size(), gpu_refs.data(), (int32_t)gpu_refs.size(), &nn);
+        if (rc != RT_OK || rt_last_build_timing(ctx, &build_ms) != RT_OK) {
+            std::fprintf(stderr, "rt_build_bvh: %s\n", rt_last_error(ctx));
+            return 1;
+        }
+        bv.nodes = gpu_nodes.data();
+        bv.num_nodes = nn;
+        bv.tri_indices = gpu_refs.data();
+        bv.num_tri_indices = ntri;
+        bvh_s = std::chrono::duration<double>(clk::now() - tg).count();
+    }
     rc = rt_upload_scene(ctx, mv.vertices, mv.num_vertices, mv.indices, mv.num_indices, bv.nodes, bv.num_nodes,
                          bv.tri_indices, bv.num_tri_indices, mv.normals, mv.num_normals, mv.normals_indices,
                          mv.materials, mv.num_materials, mv.tri_to_material);
@@ -232,14 +261,16 @@ int main(int argc, char** argv) {
     const double wall = std::chrono::duration<double>(clk::now() - t0).count();
     char anim[64] = "";   // --animate only: the JSON line is otherwise as ever
     if (a.animate) std::snprintf(anim, sizeof anim, ", \"update_ms_mean\": %.4f", update_ms_sum / total);
+    char built[64] = "";  // --gpu-build only
+    if (a.gpu_build) std::snprintf(built, sizeof built, ", \"build_ms\": %.4f", build_ms);
     std::printf("{\"frames\": %d, \"width\": %u, \"height\": %u, \"depth\": %d, \"fps\": %.2f, \"ms_per_frame\": %.4f, "
                 "\"kernel_ms_per_frame\": %.4f, \"triangles\": %d, \"bvh_nodes\": %d, \"bvh_cached\": %s, "
-                "\"bvh_seconds\": %.3f, \"contexts\": %d, \"frames_per_call\": %d%s}\n",
+                "\"bvh_seconds\": %.3f, \"contexts\": %d, \"frames_per_call\": %d%s%s}\n",
                 total, a.w, a.h, a.depth, total / wall, 1e3 * wall / total, kernel_ms_sum / total,
-                mv.num_indices / 3, bv.num_nodes, cached ? "true" : "false", bvh_s, nctx, a.batch, anim);
+                mv.num_indices / 3, bv.num_nodes, cached ? "true" : "false", bvh_s, nctx, a.batch, anim, built);
     rt_camera_destroy(cam);
     for (rt_ctx* c : ctxs) rt_destroy(c);
-    rt_bvh_destroy(bvh);
+    if (bvh) rt_bvh_destroy(bvh);
     rt_mesh_destroy(mesh);
     return 0;
 }

@@ -93,11 +93,11 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_scene_image_load", "rt_fetch_counts", "rt_gather_peak", "rt_chase_peak", "rt_chase_latency", "rt_wave_timeline", "rt_last_timing", "rt_timing_average", "rt_last_deferred", "rt_overflow_count", "rt_destroy", "rt_last_error",
                "rt_abi_version",
                "rt_refit_nodes", "rt_update_vertices", "rt_update_vertices_device", "rt_scene_bounds",
-               "rt_last_update_timing"]
+               "rt_last_update_timing", "rt_build_bvh", "rt_build_bvh_device", "rt_last_build_timing"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
                 "rt_mesh_load_dae", "rt_mesh_save_dae",
                 "rt_mesh_gen_cornell", "rt_mesh_gen_torus_knot", "rt_mesh_gen_heightfield", "rt_mesh_gen_random",
-                "rt_mesh_append_grid", "rt_bvh_build", "rt_bvh_build_sbvh", "rt_bvh_view_get", "rt_bvh_destroy", "rt_bvh_save",
+                "rt_mesh_append_grid", "rt_bvh_build", "rt_bvh_build_sbvh", "rt_bvh_build_lbvh", "rt_bvh_view_get", "rt_bvh_destroy", "rt_bvh_save",
                 "rt_bvh_load", "rt_camera_params", "rt_camera_create", "rt_camera_destroy", "rt_camera_add_rotate",
                 "rt_camera_add_radius", "rt_camera_frame_params"]
 
@@ -177,6 +177,10 @@ def lib() -> C.CDLL:
             "rt_update_vertices_device": (C.c_int, [vp, vp, i32, vp, i32, vp]),
             "rt_scene_bounds": (C.c_int, [vp, C.POINTER(rt_float4), C.POINTER(rt_float4)]),
             "rt_last_update_timing": (C.c_int, [vp, C.POINTER(f32)]),
+            "rt_build_bvh": (C.c_int, [vp, vp, i32, vp, i32, i32, vp, i32, vp, i32, C.POINTER(i32)]),
+            "rt_build_bvh_device": (C.c_int, [vp, vp, i32, vp, i32, i32, vp, i32, vp, i32, C.POINTER(i32), vp]),
+            "rt_last_build_timing": (C.c_int, [vp, C.POINTER(f32)]),
+            "rt_bvh_build_lbvh": (C.c_int, [vp, i32, C.POINTER(vp)]),
             "rt_mesh_create": (vp, []),
             "rt_mesh_destroy": (None, [vp]),
             "rt_mesh_view_get": (C.c_int, [vp, C.POINTER(rt_mesh_view)]),
@@ -397,6 +401,13 @@ class Mesh:
         _check(lib().rt_bvh_build_sbvh(self._h, threads, C.byref(h)))
         return Bvh(h)
 
+    def build_lbvh(self, max_leaf: int = 2) -> "Bvh":
+        """rt_bvh_build_lbvh: the linear BVH of DESIGN.md 15 on the host -- the same bytes
+        Renderer.build_bvh builds on the GPU.  max_leaf 2 rendered C3 fastest."""
+        h = C.c_void_p()
+        _check(lib().rt_bvh_build_lbvh(self._h, max_leaf, C.byref(h)))
+        return Bvh(h)
+
     def load_bvh(self, path: str) -> "Bvh":
         h = C.c_void_p()
         _check(lib().rt_bvh_load(self._h, path.encode(), C.byref(h)))
@@ -512,6 +523,50 @@ class Renderer:
         """rt_last_update_timing: kernel time of the last update_vertices (ms)."""
         ms = C.c_float()
         _check(lib().rt_last_update_timing(self._h, C.byref(ms)), self._h)
+        return ms.value
+
+    def build_bvh(self, vertices, indices, max_leaf: int = 2, num_vertices: Optional[int] = None,
+                  num_indices: Optional[int] = None):
+        """rt_build_bvh: the linear BVH of DESIGN.md 15 built on the GPU -> (nodes float32
+        (nn, 12), tri_indices int32 (ntri,)), the arrays Scene and upload take.  `vertices`: float32
+        (nv, 4), `indices`: int32 (3 * ntri,).  Either may instead be a (device pointer, stream)
+        pair, as update_vertices accepts: the build then runs through rt_build_bvh_device (a numpy
+        argument is copied to the device first), and a device array needs its count (num_vertices /
+        num_indices).  The uploaded scene is not touched."""
+        dev_v, dev_i = isinstance(vertices, tuple), isinstance(indices, tuple)
+        v = None if dev_v else np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 4)
+        i = None if dev_i else np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
+        nv = int(num_vertices) if dev_v else v.shape[0]
+        nidx = int(num_indices) if dev_i else i.size
+        ntri = max(nidx // 3, 1)
+        nn = C.c_int32()
+        if not (dev_v or dev_i):
+            nodes = np.zeros((2 * ntri - 1, 12), np.float32)
+            refs = np.zeros(ntri, np.int32)
+            _check(lib().rt_build_bvh(self._h, _ptr(v), nv, _ptr(i), nidx, max_leaf, _ptr(nodes), nodes.shape[0],
+                                      _ptr(refs), refs.size, C.byref(nn)), self._h)
+            return nodes[:nn.value].copy(), refs[:max(nidx // 3, 0)]
+        import torch
+        dev = f"cuda:{self.device}"
+        stream = (vertices if dev_v else indices)[1]
+        if dev_v and dev_i and indices[1] != stream:
+            raise ValueError("build_bvh: device vertices and indices must be produced on one stream")
+        t_v = None if dev_v else torch.from_numpy(v).to(dev)   # a host array joins the device one
+        t_i = None if dev_i else torch.from_numpy(i).to(dev)
+        d_v = vertices[0] if dev_v else t_v.data_ptr()
+        d_i = indices[0] if dev_i else t_i.data_ptr()
+        d_nodes = torch.zeros((2 * ntri - 1, 12), dtype=torch.float32, device=dev)
+        d_refs = torch.zeros(ntri, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        _check(lib().rt_build_bvh_device(self._h, C.c_void_p(d_v), nv, C.c_void_p(d_i), nidx, max_leaf,
+                                         C.c_void_p(d_nodes.data_ptr()), d_nodes.shape[0], C.c_void_p(d_refs.data_ptr()),
+                                         d_refs.numel(), C.byref(nn), C.c_void_p(stream or None)), self._h)
+        return d_nodes[:nn.value].cpu().numpy(), d_refs[:max(nidx // 3, 0)].cpu().numpy()
+
+    def last_build_ms(self) -> float:
+        """rt_last_build_timing: kernel time of the last build_bvh (ms)."""
+        ms = C.c_float()
+        _check(lib().rt_last_build_timing(self._h, C.byref(ms)), self._h)
         return ms.value
 
     def scene_image_size(self) -> int:
