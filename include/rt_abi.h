@@ -207,6 +207,39 @@ int rt_build_bvh_device(rt_ctx* ctx, const rt_float4* d_verts, int32_t nv, const
                         int32_t* num_nodes, void* stream);
 int rt_last_build_timing(rt_ctx* ctx, float* total_ms);
 
+/* A renderable scene built on the GPU: rt_build_bvh's tree and rt_upload_scene's
+ * device records in one call, with no host round trip.  After RT_OK the context's scene is the one
+ * rt_upload_scene builds from the same mesh arrays and the nodes / refs rt_build_bvh (equivalently
+ * rt_bvh_build_lbvh) gives for (verts, idx, max_leaf): the same scene image word for word, the same
+ * rt_scene_bounds, refit data present (rt_update_vertices works on it).  The caller's arrays are
+ * copied; the caller keeps ownership.
+ *
+ * rt_build_scene: host arrays.  rt_build_scene_device: device arrays produced on `stream` (NULL =
+ *   the null stream), d_verts and d_normals 16-byte aligned; the materials are a host array in both.
+ *   Both are synchronous: they run on the context's stream, wait for the frames in flight before
+ *   the old scene is replaced and return when the new one is renderable.  On any failure the
+ *   previous scene, if any, is untouched and still renders.  The device arrays of a scene that a
+ *   later rt_build_scene replaces stay with the context for the call after it (a mesh rebuilt again
+ *   and again allocates nothing); rt_destroy frees them.
+ * RT_ERR_INVALID_ARG, before any GPU work: a NULL pointer, nidx % 3 != 0, n = nidx / 3 outside
+ *   [1, 2^25], max_leaf outside 1..8, nv, nnorm or nmat <= 0.  RT_ERR_BAD_SCENE: a vertex, normal or
+ *   material index outside its array -- found on the host by rt_build_scene, by the first kernel
+ *   for device arrays (no kernel reads through such an index, nothing after that kernel runs); the
+ *   message names the array.  The context stays usable after either.
+ * rt_last_scene_build_timing: HIP-event time (ms) from the first to the last kernel of the
+ *   context's last successful call, the short host reads in between included.
+ * rt_refit_level_counts (diagnostics): the inner records per height of the scene's refit plan,
+ *   height 1 first; *heights = their number, counts[0 .. min(cap, *heights)) written.  Works for any
+ *   scene with refit data (rt_upload_scene's too), else RT_ERR_BAD_SCENE. */
+int rt_build_scene(rt_ctx* ctx, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx, int32_t max_leaf,
+                   const rt_float4* normals, int32_t nnorm, const int32_t* normal_idx,
+                   const rt_material* mats, int32_t nmat, const int32_t* tri_to_mat);
+int rt_build_scene_device(rt_ctx* ctx, const rt_float4* d_verts, int32_t nv, const int32_t* d_idx, int32_t nidx,
+                          int32_t max_leaf, const rt_float4* d_normals, int32_t nnorm, const int32_t* d_normal_idx,
+                          const rt_material* mats /* host */, int32_t nmat, const int32_t* d_tri_to_mat, void* stream);
+int rt_last_scene_build_timing(rt_ctx* ctx, float* total_ms);
+int rt_refit_level_counts(rt_ctx* ctx, uint32_t* counts, int32_t cap, int32_t* heights);
+
 /* Multi-GPU scene distribution ("ncclBroadcast of scene buffers at load").
  * The reference uploads one scene to its one device (RayTracer.cpp:942-984); here one
  * rank builds and uploads it, packs its device layouts into ONE contiguous device

@@ -15,6 +15,10 @@ struct Scratch {
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // around the build's kernels; the caller's stream
     bool timed = false;
     uint32_t launches = 0;
+    // host copy of the last build's depth lists: the kept nodes of depth d are
+    // level_ids[depth_begin[d] .. depth_begin[d + 1]); deepest = -1 when the root is a leaf
+    uint32_t depth_begin[66] = {};
+    int deepest = -1;
 };
 
 hipError_t reserve(Scratch::Buf& b, size_t bytes);

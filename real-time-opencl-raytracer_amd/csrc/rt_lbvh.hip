@@ -343,6 +343,7 @@ int build(Scratch& S, hipStream_t s, const float4* d_verts, int32_t nv, const in
         ++launches;
         LB_HIP(hipGetLastError());
         *num_nodes = 1;
+        S.deepest = -1;
         S.launches = launches;
         return RT_OK;
     }
@@ -390,6 +391,9 @@ int build(Scratch& S, hipStream_t s, const float4* d_verts, int32_t nv, const in
     }
     LB_HIP(hipGetLastError());
     *num_nodes = (int32_t)(2 * K + 1);
+    static_assert(sizeof S.depth_begin == sizeof lv.begin, "the scratch keeps the whole table");
+    std::memcpy(S.depth_begin, lv.begin, sizeof lv.begin);
+    S.deepest = deepest;
     S.launches = launches;
     return RT_OK;
 }

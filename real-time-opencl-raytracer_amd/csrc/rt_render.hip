@@ -50,6 +50,7 @@
 #include "rt_refit.h"
 #include "refit.hpp"
 #include "rt_lbvh.h"
+#include "rt_scene_build.h"
 #include "lbvh_core.hpp"
 
 #ifndef RTK_WF_WAVES
@@ -1092,6 +1093,16 @@ struct rt_ctx {
         uint32_t launches = 0;
     } refit;
     rtlbvh::Scratch lbvh;                      // rt_build_bvh's buffers; no part of the scene
+    rtscene::Scratch sbuild;                   // rt_build_scene's buffers; no part of the scene
+    // rt_build_scene's allocations (capacities in bytes): `built` names those of the scene it built, while
+    // that scene is the context's; `spare` holds those of the scene a later call replaced, for the call
+    // after it -- a mesh rebuilt again and again allocates and frees nothing
+    struct SceneArrays {
+        enum { kRec, kTris, kShade, kLeaf, kIdx, kNormalIdx, kRefTri, kLevelIds, kLevelBegin, kOut, kVerts, kNormals, kCount };
+        void* p[kCount] = {};
+        size_t cap[kCount] = {};
+    };
+    SceneArrays built, spare;
     bool have_bounds = false;                 // rt_scene_bounds: the uploaded / refit root box
     rt_float4 bounds_min{}, bounds_max{};
     std::string err;
@@ -1227,8 +1238,10 @@ static uint64_t record_limit() {
     return lim && lim < 0x80000000ull ? lim : 0x80000000ull;
 }
 
+static bool records_split(size_t n_wnodes4, size_t n_tris4) { return (n_wnodes4 + n_tris4) * 16 >= record_limit(); }
+
 static hipError_t alloc_records(rt_ctx* c, size_t n_wnodes4, size_t n_tris4) {
-    c->split_records = (n_wnodes4 + n_tris4) * 16 >= record_limit();
+    c->split_records = records_split(n_wnodes4, n_tris4);
     if (c->split_records) {
         hipError_t e = hipMalloc((void**)&c->d_wnodes, n_wnodes4 * sizeof(float4));
         if (e != hipSuccess) { c->d_wnodes = nullptr; return e; }
@@ -1260,6 +1273,7 @@ static void free_refit(rt_ctx* c, const char* why) {
 }
 
 static void free_scene(rt_ctx* c) {
+    c->built = rt_ctx::SceneArrays{};
     free_refit(c, "no scene uploaded");
     c->have_bounds = false;
     if (c->split_records && c->d_tris) (void)hipFree(c->d_tris);
@@ -1573,6 +1587,9 @@ int rt_destroy(rt_ctx* c) {
     for (hipEvent_t& e : c->refit.ev)
         if (e) (void)hipEventDestroy(e);
     rtlbvh::release(c->lbvh);
+    rtscene::release(c->sbuild);
+    for (void* p : c->spare.p)
+        if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return RT_OK;
@@ -1955,6 +1972,256 @@ int rt_last_build_timing(rt_ctx* c, float* total_ms) {
     if (!c || !total_ms) return set_err(c, "rt_last_build_timing: invalid argument", RT_ERR_INVALID_ARG);
     if (!c->lbvh.timed) return set_err(c, "rt_last_build_timing: no successful build on this context", RT_ERR_INVALID_ARG);
     HIPC(c, hipEventElapsedTime(total_ms, c->lbvh.ev[0], c->lbvh.ev[1]));
+    return RT_OK;
+}
+
+// ---- a renderable scene built on the GPU ----
+// rt_build_bvh's tree and rt_upload_scene's records without a host round trip: the index check,
+// rtlbvh::build into context-owned scratch, then rtscene's kernels write the records into arrays
+// of their own (NewScene).  The context takes them only when everything has succeeded (after waiting for the
+// frames in flight); until then the previous scene is untouched, and it stays on any failure.
+namespace {
+using SceneArrays = rt_ctx::SceneArrays;
+
+// What a call allocates: from the spare set where that fits, else fresh.  Unless the context takes
+// it, it goes (back) to the spare set.
+struct NewScene {
+    rt_ctx* c;
+    SceneArrays arr;
+    explicit NewScene(rt_ctx* ctx) : c(ctx) {}
+    NewScene(const NewScene&) = delete;
+    NewScene& operator=(const NewScene&) = delete;
+    hipError_t take(int k, size_t bytes) {
+        bytes = std::max<size_t>(bytes, 16);
+        SceneArrays& sp = c->spare;
+        if (sp.p[k] && sp.cap[k] >= bytes) {
+            arr.p[k] = sp.p[k]; arr.cap[k] = sp.cap[k];
+            sp.p[k] = nullptr; sp.cap[k] = 0;
+            return hipSuccess;
+        }
+        const hipError_t e = hipMalloc(&arr.p[k], bytes);
+        if (e != hipSuccess) arr.p[k] = nullptr; else arr.cap[k] = bytes;
+        return e;
+    }
+    ~NewScene() {
+        for (int k = 0; k < SceneArrays::kCount; ++k) {
+            if (!arr.p[k]) continue;
+            if (!c->spare.p[k]) { c->spare.p[k] = arr.p[k]; c->spare.cap[k] = arr.cap[k]; }
+            else (void)hipFree(arr.p[k]);
+        }
+    }
+};
+}  // namespace
+
+// The arrays of a scene rt_build_scene built go to the spare set (the caller has waited for the
+// frames in flight); free_scene then finds nothing of them.
+static void stash_scene(rt_ctx* c) {
+    SceneArrays& b = c->built;
+    if (!c->have_scene || !b.p[SceneArrays::kRec] || b.p[SceneArrays::kRec] != (void*)c->d_wnodes) return;
+    for (int k = 0; k < SceneArrays::kCount; ++k) {
+        if (!b.p[k]) continue;
+        if (c->spare.p[k]) (void)hipFree(c->spare.p[k]);
+        c->spare.p[k] = b.p[k];
+        c->spare.cap[k] = b.cap[k];
+    }
+    rt_ctx::Refit& r = c->refit;
+    c->d_wnodes = nullptr; c->d_tris = nullptr; c->d_shade = nullptr; c->d_leaf = nullptr;
+    r.d_idx = r.d_normal_idx = r.d_ref_tri = nullptr;
+    r.d_level_ids = r.d_level_begin = r.d_out = nullptr;
+    if (b.p[SceneArrays::kVerts]) r.d_verts = nullptr;
+    if (b.p[SceneArrays::kNormals]) r.d_normals = nullptr;
+    b = SceneArrays{};
+}
+
+static int build_scene(rt_ctx* c, const char* who, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx,
+                       int32_t max_leaf, const rt_float4* normals, int32_t nnorm, const int32_t* normal_idx,
+                       const rt_material* mats, int32_t nmat, const int32_t* tri_to_mat, bool on_device, void* stream) {
+    if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
+    if (!verts || !idx || !normals || !normal_idx || !mats || !tri_to_mat)
+        return set_err(c, std::string(who) + ": missing array", RT_ERR_INVALID_ARG);
+    if (nv <= 0 || nnorm <= 0 || nmat <= 0) return set_err(c, std::string(who) + ": empty array", RT_ERR_INVALID_ARG);
+    if (max_leaf < 1 || max_leaf > 8) return set_err(c, std::string(who) + ": max_leaf must be 1 .. 8", RT_ERR_INVALID_ARG);
+    if (nidx <= 0 || nidx % 3 != 0 || nidx / 3 > lbvh::kMaxTris)
+        return set_err(c, std::string(who) + ": needs 1 .. 2^25 triangles, 3 indices each", RT_ERR_INVALID_ARG);
+    const int32_t n = nidx / 3;
+    if (on_device) {
+        if (((uintptr_t)verts | (uintptr_t)normals) & 15u)
+            return set_err(c, std::string(who) + ": d_verts and d_normals must be 16-byte aligned", RT_ERR_INVALID_ARG);
+    } else {
+        for (int32_t i = 0; i < nidx; ++i) {
+            if (idx[i] < 0 || idx[i] >= nv) return set_err(c, "mesh_indices out of range", RT_ERR_BAD_SCENE);
+            if (normal_idx[i] < 0 || normal_idx[i] >= nnorm) return set_err(c, "mesh_normals_indices out of range", RT_ERR_BAD_SCENE);
+        }
+        for (int32_t t = 0; t < n; ++t)
+            if (tri_to_mat[t] < 0 || tri_to_mat[t] >= nmat) return set_err(c, "tri_to_material out of range", RT_ERR_BAD_SCENE);
+    }
+    HIPC(c, hipSetDevice(c->device));
+    rtlbvh::Scratch& S = c->lbvh;
+    rtscene::Scratch& W = c->sbuild;
+    for (hipEvent_t& e : W.ev)
+        if (!e) HIPC(c, hipEventCreate(&e));
+    W.timed = false;
+    auto fail = [&](int rc, const std::string& m) {
+        (void)hipStreamSynchronize(c->stream);   // nothing of this call is still running when its arrays go
+        (void)hipGetLastError();
+        return set_err(c, m, rc);
+    };
+    auto oom = [&] { return fail(RT_ERR_OUT_OF_MEMORY, std::string(who) + ": out of device memory"); };
+
+    using A = SceneArrays;
+    NewScene ns(c);
+    if (ns.take(A::kIdx, (size_t)nidx * 4) != hipSuccess || ns.take(A::kNormalIdx, (size_t)nidx * 4) != hipSuccess ||
+        ns.take(A::kRefTri, (size_t)n * 4) != hipSuccess || ns.take(A::kOut, 32) != hipSuccess ||
+        rtlbvh::reserve(W.mats, (size_t)nmat * sizeof(rt_material)) != hipSuccess ||
+        rtlbvh::reserve(S.nodes, (size_t)(2 * (int64_t)n - 1) * sizeof(rt_bvh_node)) != hipSuccess)
+        return oom();
+    int32_t *new_idx = (int32_t*)ns.arr.p[A::kIdx], *new_normal_idx = (int32_t*)ns.arr.p[A::kNormalIdx];
+    int32_t* new_ref_tri = (int32_t*)ns.arr.p[A::kRefTri];
+    uint32_t* new_out = (uint32_t*)ns.arr.p[A::kOut];
+    const float4* d_verts = (const float4*)verts;
+    const float4* d_normals = (const float4*)normals;
+    const int32_t* d_tri_to_mat = tri_to_mat;
+    hipMemcpyKind kind = hipMemcpyDeviceToDevice;
+    if (on_device) {   // the caller's stream may still be producing the inputs
+        HIPC(c, hipEventRecord(W.ev[2], (hipStream_t)stream));
+        HIPC(c, hipStreamWaitEvent(c->stream, W.ev[2], 0));
+    } else {
+        kind = hipMemcpyHostToDevice;
+        if (ns.take(A::kVerts, (size_t)nv * sizeof(float4)) != hipSuccess ||
+            ns.take(A::kNormals, (size_t)nnorm * sizeof(float4)) != hipSuccess ||
+            rtlbvh::reserve(W.tri_to_mat, (size_t)n * 4) != hipSuccess)
+            return oom();
+        HIPC(c, hipMemcpyAsync(ns.arr.p[A::kVerts], verts, (size_t)nv * sizeof(float4), kind, c->stream));
+        HIPC(c, hipMemcpyAsync(ns.arr.p[A::kNormals], normals, (size_t)nnorm * sizeof(float4), kind, c->stream));
+        HIPC(c, hipMemcpyAsync(W.tri_to_mat.p, tri_to_mat, (size_t)n * 4, kind, c->stream));
+        d_verts = (const float4*)ns.arr.p[A::kVerts];
+        d_normals = (const float4*)ns.arr.p[A::kNormals];
+        d_tri_to_mat = (const int32_t*)W.tri_to_mat.p;
+    }
+    // the scene's own copies of the index arrays (rt_update_vertices reads them)
+    HIPC(c, hipMemcpyAsync(new_idx, idx, (size_t)nidx * 4, kind, c->stream));
+    HIPC(c, hipMemcpyAsync(new_normal_idx, normal_idx, (size_t)nidx * 4, kind, c->stream));
+    HIPC(c, hipMemcpyAsync(W.mats.p, mats, (size_t)nmat * sizeof(rt_material), hipMemcpyHostToDevice, c->stream));
+
+    HIPC(c, hipEventRecord(W.ev[0], c->stream));
+    std::string err;
+    uint32_t bad = 0;
+    int rc = rtscene::check(W, c->stream, new_idx, nv, new_normal_idx, nnorm, d_tri_to_mat, nmat, n, &bad, err);
+    if (rc != RT_OK) return fail(rc, std::string(who) + ": " + err);
+    if (bad)
+        return fail(RT_ERR_BAD_SCENE, bad & rtscene::kBadVerts     ? "mesh_indices out of range"
+                                      : bad & rtscene::kBadNormals ? "mesh_normals_indices out of range"
+                                                                   : "tri_to_material out of range");
+    int32_t nn = 0;
+    rc = rtlbvh::build(S, c->stream, d_verts, nv, new_idx, n, max_leaf, (float4*)S.nodes.p, 2 * n - 1, new_ref_tri, &nn, err);
+    if (rc != RT_OK) return fail(rc, rc == RT_ERR_BAD_SCENE ? err : std::string(who) + ": " + err);
+    const uint32_t K = (uint32_t)(nn - 1) / 2u;
+    const size_t n_wnodes4 = (size_t)std::max<uint32_t>(K, 1u) * 4, n_tris4 = (size_t)n * 3 + 1, n_shade4 = (size_t)n * 7;
+    // inner and triangle records in one allocation, or two: alloc_records' layout and rule
+    const bool split = records_split(n_wnodes4, n_tris4);
+    if (ns.take(A::kRec, (split ? n_wnodes4 : n_wnodes4 + n_tris4) * sizeof(float4)) != hipSuccess ||
+        (split && ns.take(A::kTris, n_tris4 * sizeof(float4)) != hipSuccess) ||
+        ns.take(A::kShade, n_shade4 * sizeof(float4)) != hipSuccess || ns.take(A::kLeaf, sizeof(int2)) != hipSuccess ||
+        ns.take(A::kLevelIds, (size_t)K * 4) != hipSuccess)
+        return oom();
+    float4* new_wnodes = (float4*)ns.arr.p[A::kRec];
+    float4* new_tris = split ? (float4*)ns.arr.p[A::kTris] : new_wnodes + n_wnodes4;
+    HIPC(c, hipMemsetAsync(new_tris + (size_t)n * 3, 0, sizeof(float4), c->stream));   // the trailing pad
+    HIPC(c, hipMemsetAsync(ns.arr.p[A::kLeaf], 0, sizeof(int2), c->stream));           // no escape leaves: {0, 0}
+    rtscene::Args a{};
+    a.verts = d_verts; a.normals = d_normals; a.idx = new_idx; a.normal_idx = new_normal_idx; a.tri_to_mat = d_tri_to_mat;
+    a.mats = (const float4*)W.mats.p; a.nodes = (const float4*)S.nodes.p; a.refs = new_ref_tri;
+    a.n = n; a.max_leaf = max_leaf; a.K = K;
+    a.wnodes = new_wnodes; a.tris = new_tris; a.shade = (float4*)ns.arr.p[A::kShade];
+    a.level_ids = (uint32_t*)ns.arr.p[A::kLevelIds]; a.out = new_out;
+    std::vector<uint32_t> level_begin;
+    uint32_t out[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (K == 0) {   // the root is a leaf: no inner record, four zero float4s in its place
+        HIPC(c, hipMemsetAsync(new_wnodes, 0, 4 * sizeof(float4), c->stream));
+        rc = rtscene::leaf_records(W, c->stream, a, err);
+        level_begin.assign(1, 0u);
+    } else {
+        rc = rtscene::records(W, S, c->stream, a, level_begin, err);
+    }
+    if (rc != RT_OK) return fail(rc, std::string(who) + ": " + err);
+    HIPC(c, hipEventRecord(W.ev[1], c->stream));
+    rt_bvh_node root_leaf{};
+    if (K == 0) HIPC(c, hipMemcpyAsync(&root_leaf, S.nodes.p, sizeof root_leaf, hipMemcpyDeviceToHost, c->stream));
+    else HIPC(c, hipMemcpyAsync(out, new_out, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    if (wait_stream(c->stream) != hipSuccess) return fail(RT_ERR_DEVICE, std::string(who) + ": the build's kernels failed");
+    if (K == 0) {
+        const float box[6] = {root_leaf.min.x, root_leaf.min.y, root_leaf.min.z, root_leaf.max.x, root_leaf.max.y, root_leaf.max.z};
+        std::memcpy(out + 2, box, sizeof box);
+        HIPC(c, hipMemcpy(new_out, out, sizeof out, hipMemcpyHostToDevice));
+    }
+    if (ns.take(A::kLevelBegin, 67 * 4) != hipSuccess) return oom();   // (every plan fits: at most 66 heights)
+    HIPC(c, hipMemcpy(ns.arr.p[A::kLevelBegin], level_begin.data(), level_begin.size() * 4, hipMemcpyHostToDevice));
+
+    // the context takes the new scene
+    for (auto& f : c->slots)
+        if (f.idle) HIPC(c, hipEventSynchronize(f.idle));   // frames in flight still read the old scene
+    stash_scene(c);
+    free_scene(c);
+    c->d_wnodes = new_wnodes; c->d_tris = new_tris; c->split_records = split;
+    c->d_shade = (float4*)ns.arr.p[A::kShade]; c->d_leaf = (int2*)ns.arr.p[A::kLeaf];
+    c->n_wnodes4 = n_wnodes4; c->n_tris4 = n_tris4; c->n_shade4 = n_shade4; c->n_leaf = 1;
+    c->root = K ? 0u : (rtk::kLeafBit | ((uint32_t)n << 26));   // the root's record is the breadth-first order's first
+    c->n_inner = K;
+    c->fast_div = out[0] ? 1 : 0;
+    c->clean = 1;
+    c->have_scene = true;
+    ++c->scene_gen;
+    float box[6];
+    std::memcpy(box, out + 2, sizeof box);
+    c->bounds_min = rt_float4{box[0], box[1], box[2], 1.0f};
+    c->bounds_max = rt_float4{box[3], box[4], box[5], 1.0f};
+    c->have_bounds = true;
+    rt_ctx::Refit& r = c->refit;
+    r.d_idx = new_idx; r.d_normal_idx = new_normal_idx; r.d_ref_tri = new_ref_tri;
+    r.d_level_ids = (uint32_t*)ns.arr.p[A::kLevelIds]; r.d_level_begin = (uint32_t*)ns.arr.p[A::kLevelBegin]; r.d_out = new_out;
+    r.d_verts = (float4*)ns.arr.p[A::kVerts]; r.d_normals = (float4*)ns.arr.p[A::kNormals];   // the host form's staging
+    r.level_begin = level_begin;
+    r.nv = nv; r.nnorm = nnorm; r.nref = (uint32_t)n; r.ntri = (uint32_t)n;
+    r.why.clear();
+    r.have = true;
+    c->built = ns.arr;
+    ns.arr = SceneArrays{};   // (the context took them)
+    W.timed = true;
+    return RT_OK;
+}
+
+int rt_build_scene(rt_ctx* c, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx, int32_t max_leaf,
+                   const rt_float4* normals, int32_t nnorm, const int32_t* normal_idx, const rt_material* mats, int32_t nmat,
+                   const int32_t* tri_to_mat) {
+    return build_scene(c, "rt_build_scene", verts, nv, idx, nidx, max_leaf, normals, nnorm, normal_idx, mats, nmat, tri_to_mat,
+                       false, nullptr);
+}
+
+int rt_build_scene_device(rt_ctx* c, const rt_float4* d_verts, int32_t nv, const int32_t* d_idx, int32_t nidx, int32_t max_leaf,
+                          const rt_float4* d_normals, int32_t nnorm, const int32_t* d_normal_idx, const rt_material* mats,
+                          int32_t nmat, const int32_t* d_tri_to_mat, void* stream) {
+    return build_scene(c, "rt_build_scene_device", d_verts, nv, d_idx, nidx, max_leaf, d_normals, nnorm, d_normal_idx, mats,
+                       nmat, d_tri_to_mat, true, stream);
+}
+
+int rt_last_scene_build_timing(rt_ctx* c, float* total_ms) {
+    if (!c || !total_ms) return set_err(c, "rt_last_scene_build_timing: invalid argument", RT_ERR_INVALID_ARG);
+    if (!c->sbuild.timed)
+        return set_err(c, "rt_last_scene_build_timing: no successful rt_build_scene on this context", RT_ERR_INVALID_ARG);
+    HIPC(c, hipEventElapsedTime(total_ms, c->sbuild.ev[0], c->sbuild.ev[1]));
+    return RT_OK;
+}
+
+int rt_refit_level_counts(rt_ctx* c, uint32_t* counts, int32_t cap, int32_t* heights) {
+    if (!c || !heights || cap < 0 || (cap > 0 && !counts))
+        return set_err(c, "rt_refit_level_counts: invalid argument", RT_ERR_INVALID_ARG);
+    if (!c->have_scene) return set_err(c, "rt_refit_level_counts: no scene uploaded", RT_ERR_NO_SCENE);
+    const rt_ctx::Refit& r = c->refit;
+    if (!r.have || r.level_begin.empty())
+        return set_err(c, "rt_refit_level_counts: the scene has no refit data (" + r.why + ")", RT_ERR_BAD_SCENE);
+    const int32_t h = (int32_t)r.level_begin.size() - 1;
+    for (int32_t i = 0; i < h && i < cap; ++i) counts[i] = r.level_begin[i + 1] - r.level_begin[i];
+    *heights = h;
     return RT_OK;
 }
 

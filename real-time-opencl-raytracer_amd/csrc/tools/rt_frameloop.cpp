@@ -13,12 +13,14 @@
 // become base * (1 + f / 64) through rt_update_vertices (the records and the BVH boxes are refitted on
 // the GPU) and the frame's scene box is rt_scene_bounds'.  With --gpu-build the scene's BVH is
 // built on the GPU (rt_build_bvh, leaves of at most --max-leaf triangles, default 2) instead of by the
-// host builder, and the summary reports build_ms, the build's kernel time.
+// host builder, and the summary reports build_ms, the build's kernel time.  With --gpu-scene the whole
+// scene -- that BVH and the device records -- is built on the GPU from the mesh (rt_build_scene, no host
+// builder and no rt_upload_scene), and the summary reports scene_build_ms, the call's kernel time.
 //
 //   rt_frameloop [--dae F | --obj F | --scene cornell|knot|heightfield] [--bvh-cache F]
 //                [--width W] [--height H] [--depth D] [--frames N] [--drag DX DY]
 //                [--ppm-dir DIR] [--ppm-every K] [--device I] [--flags F] [--gpus N | --devices a,b,...]
-//                [--batch K] [--animate] [--gpu-build [--max-leaf N]]
+//                [--batch K] [--animate] [--gpu-build | --gpu-scene [--max-leaf N]]
 //
 // Prints "N.N fps" lines and a final JSON summary.
 #include <algorithm>
@@ -43,6 +45,7 @@ struct Args {
     std::vector<int> devices;   // rt_render_tiled over these (empty: rt_render on --device)
     bool animate = false;       // rt_update_vertices before every frame
     bool gpu_build = false;     // rt_build_bvh instead of the host builder
+    bool gpu_scene = false;     // rt_build_scene instead of the host builder and rt_upload_scene
     int max_leaf = 2;
 };
 
@@ -52,7 +55,7 @@ int usage() {
                  "                    [--width W] [--height H] [--depth D] [--frames N] [--drag DX DY]\n"
                  "                    [--ppm-dir DIR] [--ppm-every K] [--device I] [--flags F]\n"
                  "                    [--gpus N | --devices a,b,...] [--batch K] [--animate]\n"
-                 "                    [--gpu-build [--max-leaf N]]\n");
+                 "                    [--gpu-build | --gpu-scene [--max-leaf N]]\n");
     return 2;
 }
 
@@ -76,6 +79,7 @@ bool parse(int argc, char** argv, Args& a) {
         else if (k == "--batch" && need(1)) a.batch = std::atoi(argv[++i]);
         else if (k == "--animate") a.animate = true;
         else if (k == "--gpu-build") a.gpu_build = true;
+        else if (k == "--gpu-scene") a.gpu_scene = true;
         else if (k == "--max-leaf" && need(1)) a.max_leaf = std::atoi(argv[++i]);
         else if (k == "--gpus" && need(1)) {
             const int n = std::atoi(argv[++i]);
@@ -98,7 +102,7 @@ bool parse(int argc, char** argv, Args& a) {
     return a.w > 0 && a.h > 0 && a.frames > 0 && a.depth >= 0 && a.depth <= RT_MAX_DEPTH && a.batch >= 1 &&
            a.batch <= RT_MAX_BATCH && (a.batch == 1 || a.devices.size() <= 1) &&
            (!a.animate || (a.batch == 1 && a.devices.size() <= 1)) &&   // the update is one context's
-           a.max_leaf >= 1 && a.max_leaf <= 8;
+           a.max_leaf >= 1 && a.max_leaf <= 8 && !(a.gpu_build && a.gpu_scene);
 }
 
 // Packed pixels are b<<16 | g<<8 | r (volumeRender.cl:186-195); row 0 is the first image row.
@@ -140,8 +144,9 @@ int main(int argc, char** argv) {
     const auto tb = clk::now();
     rt_bvh* bvh = nullptr;
     bool cached = false;
-    if (!a.gpu_build && !a.bvh_cache.empty() && rt_bvh_load(mesh, a.bvh_cache.c_str(), &bvh) == RT_OK) cached = true;
-    if (!bvh && !a.gpu_build) {
+    const bool host_bvh = !a.gpu_build && !a.gpu_scene;
+    if (host_bvh && !a.bvh_cache.empty() && rt_bvh_load(mesh, a.bvh_cache.c_str(), &bvh) == RT_OK) cached = true;
+    if (!bvh && host_bvh) {
         if ((rc = rt_bvh_build_sbvh(mesh, 0, &bvh)) != RT_OK) { std::fprintf(stderr, "bvh build failed\n"); return 1; }
         if (!a.bvh_cache.empty()) rt_bvh_save(bvh, mesh, a.bvh_cache.c_str());
     }
@@ -181,10 +186,22 @@ int main(int argc, char** argv) {
         bv.num_tri_indices = ntri;
         bvh_s = std::chrono::duration<double>(clk::now() - tg).count();
     }
-    rc = rt_upload_scene(ctx, mv.vertices, mv.num_vertices, mv.indices, mv.num_indices, bv.nodes, bv.num_nodes,
-                         bv.tri_indices, bv.num_tri_indices, mv.normals, mv.num_normals, mv.normals_indices,
-                         mv.materials, mv.num_materials, mv.tri_to_material);
-    if (rc != RT_OK) { std::fprintf(stderr, "rt_upload_scene: %s\n", rt_last_error(ctx)); return 1; }
+    float scene_build_ms = 0.0f;
+    if (a.gpu_scene) {   // mesh arrays in, a renderable scene out: no BVH or record ever in host memory
+        const auto tg = clk::now();
+        rc = rt_build_scene(ctx, mv.vertices, mv.num_vertices, mv.indices, mv.num_indices, a.max_leaf, mv.normals,
+                            mv.num_normals, mv.normals_indices, mv.materials, mv.num_materials, mv.tri_to_material);
+        if (rc != RT_OK || rt_last_scene_build_timing(ctx, &scene_build_ms) != RT_OK) {
+            std::fprintf(stderr, "rt_build_scene: %s\n", rt_last_error(ctx));
+            return 1;
+        }
+        bvh_s = std::chrono::duration<double>(clk::now() - tg).count();
+    } else {
+        rc = rt_upload_scene(ctx, mv.vertices, mv.num_vertices, mv.indices, mv.num_indices, bv.nodes, bv.num_nodes,
+                             bv.tri_indices, bv.num_tri_indices, mv.normals, mv.num_normals, mv.normals_indices,
+                             mv.materials, mv.num_materials, mv.tri_to_material);
+        if (rc != RT_OK) { std::fprintf(stderr, "rt_upload_scene: %s\n", rt_last_error(ctx)); return 1; }
+    }
     for (size_t k = 1; k < ctxs.size(); ++k)   // the scene once per node: copied, not re-uploaded
         if ((rc = rt_scene_copy(ctxs[k], ctx)) != RT_OK) {
             std::fprintf(stderr, "rt_scene_copy: %s\n", rt_last_error(ctxs[k]));
@@ -263,6 +280,7 @@ int main(int argc, char** argv) {
     if (a.animate) std::snprintf(anim, sizeof anim, ", \"update_ms_mean\": %.4f", update_ms_sum / total);
     char built[64] = "";  // --gpu-build only
     if (a.gpu_build) std::snprintf(built, sizeof built, ", \"build_ms\": %.4f", build_ms);
+    if (a.gpu_scene) std::snprintf(built, sizeof built, ", \"scene_build_ms\": %.4f", scene_build_ms);   // --gpu-scene only
     std::printf("{\"frames\": %d, \"width\": %u, \"height\": %u, \"depth\": %d, \"fps\": %.2f, \"ms_per_frame\": %.4f, "
                 "\"kernel_ms_per_frame\": %.4f, \"triangles\": %d, \"bvh_nodes\": %d, \"bvh_cached\": %s, "
                 "\"bvh_seconds\": %.3f, \"contexts\": %d, \"frames_per_call\": %d%s%s}\n",

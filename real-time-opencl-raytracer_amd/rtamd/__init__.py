@@ -93,7 +93,8 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_scene_image_load", "rt_fetch_counts", "rt_gather_peak", "rt_chase_peak", "rt_chase_latency", "rt_wave_timeline", "rt_last_timing", "rt_timing_average", "rt_last_deferred", "rt_overflow_count", "rt_destroy", "rt_last_error",
                "rt_abi_version",
                "rt_refit_nodes", "rt_update_vertices", "rt_update_vertices_device", "rt_scene_bounds",
-               "rt_last_update_timing", "rt_build_bvh", "rt_build_bvh_device", "rt_last_build_timing"]
+               "rt_last_update_timing", "rt_build_bvh", "rt_build_bvh_device", "rt_last_build_timing",
+               "rt_build_scene", "rt_build_scene_device", "rt_last_scene_build_timing", "rt_refit_level_counts"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
                 "rt_mesh_load_dae", "rt_mesh_save_dae",
                 "rt_mesh_gen_cornell", "rt_mesh_gen_torus_knot", "rt_mesh_gen_heightfield", "rt_mesh_gen_random",
@@ -180,6 +181,10 @@ def lib() -> C.CDLL:
             "rt_build_bvh": (C.c_int, [vp, vp, i32, vp, i32, i32, vp, i32, vp, i32, C.POINTER(i32)]),
             "rt_build_bvh_device": (C.c_int, [vp, vp, i32, vp, i32, i32, vp, i32, vp, i32, C.POINTER(i32), vp]),
             "rt_last_build_timing": (C.c_int, [vp, C.POINTER(f32)]),
+            "rt_build_scene": (C.c_int, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, i32, vp]),
+            "rt_build_scene_device": (C.c_int, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]),
+            "rt_last_scene_build_timing": (C.c_int, [vp, C.POINTER(f32)]),
+            "rt_refit_level_counts": (C.c_int, [vp, C.POINTER(u32), i32, C.POINTER(i32)]),
             "rt_bvh_build_lbvh": (C.c_int, [vp, i32, C.POINTER(vp)]),
             "rt_mesh_create": (vp, []),
             "rt_mesh_destroy": (None, [vp]),
@@ -568,6 +573,69 @@ class Renderer:
         ms = C.c_float()
         _check(lib().rt_last_build_timing(self._h, C.byref(ms)), self._h)
         return ms.value
+
+    def build_scene(self, scene, max_leaf: int = 2, num_vertices: Optional[int] = None,
+                    num_indices: Optional[int] = None, num_normals: Optional[int] = None) -> None:
+        """rt_build_scene: the scene of DESIGN.md 16 -- build_bvh's tree and upload's records in one
+        call on the GPU.  `scene`: a Scene, a Mesh or a dict with vertices (nv, 4), indices (3 * ntri,),
+        normals (nn, 4), normals_indices, materials (nm, 44) and tri_to_material (nodes / tri_indices,
+        if present, are ignored).  Any of them but the materials may instead be a (device pointer,
+        stream) pair, as build_bvh accepts: the call then goes through rt_build_scene_device (numpy
+        arguments are copied to the device first; all pairs name one stream), and device vertices,
+        indices and normals need their counts (num_vertices / num_indices / num_normals)."""
+        d = scene.arrays() if hasattr(scene, "arrays") else dict(scene)
+        spec = [("vertices", np.float32, (-1, 4)), ("indices", np.int32, (-1,)), ("normals", np.float32, (-1, 4)),
+                ("normals_indices", np.int32, (-1,)), ("tri_to_material", np.int32, (-1,))]
+        dev = {k: isinstance(d[k], tuple) for k, _, _ in spec}
+        host = {k: None if dev[k] else np.ascontiguousarray(d[k], dtype=dt).reshape(shape) for k, dt, shape in spec}
+        mats = np.ascontiguousarray(d["materials"], dtype=np.float32).reshape(-1, 44)
+        nv = int(num_vertices) if dev["vertices"] else host["vertices"].shape[0]
+        nidx = int(num_indices) if dev["indices"] else host["indices"].size
+        nnorm = int(num_normals) if dev["normals"] else host["normals"].shape[0]
+        for k in ("normals_indices", "tri_to_material"):   # a short host array would be read past its end
+            want = nidx if k == "normals_indices" else nidx // 3
+            if host[k] is not None and host[k].size != want:
+                raise ValueError(f"build_scene: {k} has {host[k].size} entries, the mesh needs {want}")
+
+        class _Counts:   # what update_vertices reads of an uploaded Scene
+            vertices = np.empty((nv, 0))
+            normals = np.empty((nnorm, 0))
+
+        if not any(dev.values()):
+            _check(lib().rt_build_scene(self._h, _ptr(host["vertices"]), nv, _ptr(host["indices"]), nidx, max_leaf,
+                                        _ptr(host["normals"]), nnorm, _ptr(host["normals_indices"]), _ptr(mats),
+                                        mats.shape[0], _ptr(host["tri_to_material"])), self._h)
+            self._scene_keepalive = _Counts
+            return
+        import torch
+        streams = {d[k][1] for k in dev if dev[k]}
+        if len(streams) != 1:
+            raise ValueError("build_scene: the device arrays must be produced on one stream")
+        stream = streams.pop()
+        device = f"cuda:{self.device}"
+        keep = {k: torch.from_numpy(host[k]).to(device) for k in dev if not dev[k]}   # host arrays join the device ones
+        ptr = {k: d[k][0] if dev[k] else keep[k].data_ptr() for k in dev}
+        torch.cuda.synchronize(device)
+        _check(lib().rt_build_scene_device(self._h, C.c_void_p(ptr["vertices"]), nv, C.c_void_p(ptr["indices"]), nidx,
+                                           max_leaf, C.c_void_p(ptr["normals"]), nnorm,
+                                           C.c_void_p(ptr["normals_indices"]), _ptr(mats), mats.shape[0],
+                                           C.c_void_p(ptr["tri_to_material"]), C.c_void_p(stream or None)), self._h)
+        self._scene_keepalive = _Counts
+
+    def last_scene_build_ms(self) -> float:
+        """rt_last_scene_build_timing: kernel time of the last build_scene (ms)."""
+        ms = C.c_float()
+        _check(lib().rt_last_scene_build_timing(self._h, C.byref(ms)), self._h)
+        return ms.value
+
+    def refit_level_counts(self) -> np.ndarray:
+        """rt_refit_level_counts: inner records per height of the scene's refit plan (height 1 first)."""
+        h = C.c_int32()
+        _check(lib().rt_refit_level_counts(self._h, None, 0, C.byref(h)), self._h)
+        counts = np.zeros(max(h.value, 1), np.uint32)
+        _check(lib().rt_refit_level_counts(self._h, counts.ctypes.data_as(C.POINTER(C.c_uint32)), counts.size,
+                                           C.byref(h)), self._h)
+        return counts[:h.value]
 
     def scene_image_size(self) -> int:
         """Bytes of this ctx's scene image (rt_scene_image_size)."""
