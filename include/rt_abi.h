@@ -199,7 +199,18 @@ int rt_last_update_timing(rt_ctx* ctx, float* total_ms);
  *   the first kernel for device arrays (no kernel reads a vertex through such an index, and nothing
  *   after that kernel runs).  The context stays usable after either.
  * rt_last_build_timing: HIP-event time (ms) from the first to the last kernel of the context's
- *   last successful build, the two short host reads in between (index flag, depth counts) included. */
+ *   last successful build, the two short host reads in between (index flag, depth counts) included.
+ *
+ * RT_BUILD_EXTENT_KEYS, ORed into max_leaf of rt_build_bvh, rt_build_bvh_device,
+ *   rt_build_scene, rt_build_scene_device and rt_bvh_build_lbvh: extent-aware Morton keys.  The
+ *   per-axis keys give every axis 13 bits whatever its extent, so a flat mesh spends every third
+ *   split on its thin axis.  With the flag the 39 bits go, one at a time, to the axis whose cells
+ *   are the widest at that point (extent halved per bit already given; ties to the lowest axis; at
+ *   most 20 bits per axis; an extent that is not a positive finite number counts as 0), and an
+ *   axis with b bits has 2^b cells.  Three equal extents give the per-axis keys.  Everything after
+ *   the sort is unchanged.  max_leaf & 0xFF must still be 1..8 and any other bit is
+ *   RT_ERR_INVALID_ARG; without the flag every output byte is what it was. */
+#define RT_BUILD_EXTENT_KEYS 0x100
 int rt_build_bvh(rt_ctx* ctx, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx, int32_t max_leaf,
                  rt_bvh_node* nodes, int32_t node_cap, int32_t* refs, int32_t ref_cap, int32_t* num_nodes);
 int rt_build_bvh_device(rt_ctx* ctx, const rt_float4* d_verts, int32_t nv, const int32_t* d_idx, int32_t nidx,
@@ -230,7 +241,18 @@ int rt_last_build_timing(rt_ctx* ctx, float* total_ms);
  *   context's last successful call, the short host reads in between included.
  * rt_refit_level_counts (diagnostics): the inner records per height of the scene's refit plan,
  *   height 1 first; *heights = their number, counts[0 .. min(cap, *heights)) written.  Works for any
- *   scene with refit data (rt_upload_scene's too), else RT_ERR_BAD_SCENE. */
+ *   scene with refit data (rt_upload_scene's too), else RT_ERR_BAD_SCENE.
+ * rt_scene_sah: the surface-area-heuristic cost of the scene as it stands on the
+ *   GPU -- after rt_upload_scene, rt_build_scene, rt_update_vertices, rt_scene_image_load or
+ *   rt_scene_copy -- computed by two kernels from the inner records and the escape-leaf table.
+ *   With hA(box) = (dx*dy + dy*dz) + dz*dx in float: *root_area = hA of rt_scene_bounds' box (a
+ *   scene from rt_scene_image_load has none: the union of the root record's two child boxes);
+ *   *inner_area = *root_area + the sum of hA(child box) over every child slot that refers to an
+ *   inner record; *leaf_area_tris = the sum of hA(child box) * triangle references over every child
+ *   slot that holds a leaf (empty leaves and malformed references add nothing).  Sums in double, in
+ *   a fixed order.  A root-leaf scene gives 0 and *root_area * n.  The usual normalised cost is
+ *   (c_inner * *inner_area + c_tri * *leaf_area_tris) / *root_area.  Synchronous on the context's
+ *   stream, read-only; frames in flight are not waited for.  RT_ERR_NO_SCENE without a scene. */
 int rt_build_scene(rt_ctx* ctx, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx, int32_t max_leaf,
                    const rt_float4* normals, int32_t nnorm, const int32_t* normal_idx,
                    const rt_material* mats, int32_t nmat, const int32_t* tri_to_mat);
@@ -239,6 +261,7 @@ int rt_build_scene_device(rt_ctx* ctx, const rt_float4* d_verts, int32_t nv, con
                           const rt_material* mats /* host */, int32_t nmat, const int32_t* d_tri_to_mat, void* stream);
 int rt_last_scene_build_timing(rt_ctx* ctx, float* total_ms);
 int rt_refit_level_counts(rt_ctx* ctx, uint32_t* counts, int32_t cap, int32_t* heights);
+int rt_scene_sah(rt_ctx* ctx, double* inner_area, double* leaf_area_tris, double* root_area);
 
 /* Multi-GPU scene distribution ("ncclBroadcast of scene buffers at load").
  * The reference uploads one scene to its one device (RayTracer.cpp:942-984); here one

@@ -90,7 +90,9 @@ int rt_bvh_build_sbvh(const rt_mesh* m, int32_t num_threads, rt_bvh** out);
  * leaves, boxes fitted bottom-up.  Byte for byte what rt_build_bvh (rt_abi.h) builds on the GPU;
  * same BVH_Node_ / tri_indices layout as the other builders (BVH_Cuda.h:87-137), root = node 0,
  * but the node order is its own (kept nodes, then leaves), not pre-order.  Every triangle is
- * kept.  RT_ERR_INVALID_ARG: max_leaf outside 1..8, no triangle or more than 2^25. */
+ * kept.  max_leaf | RT_BUILD_EXTENT_KEYS (rt_abi.h): the extent-aware keys of DESIGN.md 17, as on
+ * the GPU.  RT_ERR_INVALID_ARG: max_leaf & 0xFF outside 1..8 or any other bit set, no triangle or
+ * more than 2^25. */
 int rt_bvh_build_lbvh(const rt_mesh* m, int32_t max_leaf, rt_bvh** out);
 int rt_bvh_view_get(const rt_bvh* b, rt_bvh_view* out);
 void rt_bvh_destroy(rt_bvh* b);

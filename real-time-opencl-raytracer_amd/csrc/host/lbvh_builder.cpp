@@ -3,7 +3,9 @@
 //
 //   boxes    lo / hi of every triangle (fminf / fmaxf over its vertices), c2 = lo + hi
 //   bounds   cmin / cmax of c2 over all triangles
-//   keys     13-bit cells per axis -> morton39 << 25 | triangle (lbvh_core.hpp); sorted ascending
+//   keys     cells per axis -> morton39 << 25 | triangle (lbvh_core.hpp); sorted ascending.  The
+//            key plan says which axis gives which Morton bit: 13 bits per axis in turn, or with
+//            RT_BUILD_EXTENT_KEYS in max_leaf the extent-aware plan of DESIGN.md 17
 //   tree     the binary radix tree over the sorted keys (Karras 2012), node by node
 //   collapse a radix node is kept iff its range holds more than max_leaf positions; a child of a
 //            kept node that is not kept is ONE leaf over its range
@@ -20,6 +22,8 @@
 
 #include "lbvh_core.hpp"
 #include "rt_handles.hpp"
+
+static_assert(lbvh::kExtentKeys == RT_BUILD_EXTENT_KEYS, "lbvh_core.hpp restates the ABI's flag");
 
 namespace rtamd {
 
@@ -75,7 +79,7 @@ rt_bvh_node leaf_node(int32_t first, int32_t count) {
 
 }  // namespace
 
-int build_lbvh(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx, int max_leaf, Bvh& out,
+int build_lbvh(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx, int max_leaf_arg, Bvh& out,
                std::string& err) {
     const auto t0 = std::chrono::steady_clock::now();
     out = Bvh();
@@ -83,7 +87,12 @@ int build_lbvh(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t n
         err = "lbvh: needs vertices and 1 .. 2^25 triangles (3 indices each)";
         return RT_ERR_INVALID_ARG;
     }
-    if (max_leaf < 1 || max_leaf > 8) { err = "lbvh: max_leaf must be 1 .. 8"; return RT_ERR_INVALID_ARG; }
+    int32_t max_leaf = 0;
+    bool extent_keys = false;
+    if (!lbvh::split_max_leaf(max_leaf_arg, max_leaf, extent_keys)) {
+        err = "lbvh: max_leaf must be 1 .. 8 (| RT_BUILD_EXTENT_KEYS)";
+        return RT_ERR_INVALID_ARG;
+    }
     for (int32_t i = 0; i < nidx; ++i)
         if (idx[i] < 0 || idx[i] >= nv) { err = "lbvh: mesh_indices out of range"; return RT_ERR_BAD_SCENE; }
     const int32_t n = nidx / 3;
@@ -103,12 +112,9 @@ int build_lbvh(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t n
             cmax[a] = t ? fmaxf(cmax[a], c) : c;
         }
     }
+    const lbvh::KeyPlan plan = extent_keys ? lbvh::extent_plan(cmin, cmax) : lbvh::axis_plan();
     std::vector<uint64_t> keys((size_t)n);
-    for (int32_t t = 0; t < n; ++t) {
-        const float* c = &c2[(size_t)t * 3];
-        keys[t] = lbvh::key(lbvh::cell(c[0], cmin[0], cmax[0]), lbvh::cell(c[1], cmin[1], cmax[1]),
-                            lbvh::cell(c[2], cmin[2], cmax[2]), (uint32_t)t);
-    }
+    for (int32_t t = 0; t < n; ++t) keys[t] = lbvh::key_of(plan, &c2[(size_t)t * 3], cmin, cmax, (uint32_t)t);
     std::sort(keys.begin(), keys.end());
     out.tri_indices.resize((size_t)n);
     for (int32_t p = 0; p < n; ++p) out.tri_indices[p] = 3 * (int32_t)(keys[p] & lbvh::kIndexMask);

@@ -25,11 +25,12 @@ hipError_t reserve(Scratch::Buf& b, size_t bytes);
 void release(Scratch& s);
 
 // Builds on `s` from device arrays (n = triangles, validated by the caller: 1 .. 2^25, max_leaf
-// 1 .. 8, room for 2n - 1 nodes and n references).  Waits for `s` twice on the way (the index
-// flag, the depth counts) and returns with the last kernels enqueued: d_nodes / d_refs are
+// 1 .. 8, room for 2n - 1 nodes and n references); extent_keys: the key plan of DESIGN.md 17 in
+// place of the per-axis one.  Waits for `s` twice on the way (the index flag with cmin / cmax, the
+// depth counts) and returns with the last kernels enqueued: d_nodes / d_refs are
 // complete once `s` has drained.  RT_OK, RT_ERR_BAD_SCENE (an index outside [0, nv): nothing after the first stage
 // ran), RT_ERR_OUT_OF_MEMORY or RT_ERR_DEVICE, with `err` set.
 int build(Scratch& S, hipStream_t s, const float4* d_verts, int32_t nv, const int32_t* d_idx, int32_t n,
-          int32_t max_leaf, float4* d_nodes, int32_t node_cap, int32_t* d_refs, int32_t* num_nodes, std::string& err);
+          int32_t max_leaf, bool extent_keys, float4* d_nodes, int32_t node_cap, int32_t* d_refs, int32_t* num_nodes, std::string& err);
 
 }  // namespace rtlbvh

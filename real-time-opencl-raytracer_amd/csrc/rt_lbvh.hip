@@ -3,7 +3,8 @@
 //
 //   tri_kernel      per triangle: index check, box, c2 = lo + hi; block min / max of c2
 //   bounds_kernel   one workgroup: cmin / cmax from the blocks' partial results
-//   key_kernel      13-bit cells -> morton39 << 25 | triangle
+//   key_kernel      cells -> morton39 << 25 | triangle, the bits laid out by the key plan the host
+//                   made from cmin / cmax (per-axis, or the extent-aware plan of DESIGN.md 17)
 //   (rocprim)       device radix sort of the 64-bit keys
 //   radix_kernel    one thread per radix node (Karras 2012): range, split, each inner child's
 //                   parent, kept flag, where leaves start; tri_indices
@@ -103,14 +104,15 @@ __global__ void __launch_bounds__(kThreads) bounds_kernel(const float4* part, ui
     }
 }
 
-__global__ void __launch_bounds__(kThreads) key_kernel(const float4* c2, int32_t n, const uint32_t* ctl, uint64_t* keys) {
+__global__ void __launch_bounds__(kThreads) key_kernel(const float4* c2, int32_t n, const uint32_t* ctl, lbvh::KeyPlan plan,
+                                                       uint64_t* keys) {
     const int32_t t = (int32_t)(blockIdx.x * kThreads + threadIdx.x);
     if (t >= n) return;
-    const float4 c = c2[t];
+    const float4 c4 = c2[t];
+    const float c[3] = {c4.x, c4.y, c4.z};
     const float* cmin = reinterpret_cast<const float*>(ctl + kCmin);
     const float* cmax = reinterpret_cast<const float*>(ctl + kCmax);
-    keys[t] = lbvh::key(lbvh::cell(c.x, cmin[0], cmax[0]), lbvh::cell(c.y, cmin[1], cmax[1]),
-                        lbvh::cell(c.z, cmin[2], cmax[2]), (uint32_t)t);
+    keys[t] = lbvh::key_of(plan, c, cmin, cmax, (uint32_t)t);
 }
 
 __device__ __forceinline__ bool kept(int32_t lo, int32_t hi, int32_t max_leaf) { return hi - lo + 1 > max_leaf; }
@@ -300,7 +302,7 @@ void release(Scratch& s) {
     } while (0)
 
 int build(Scratch& S, hipStream_t s, const float4* d_verts, int32_t nv, const int32_t* d_idx, int32_t n, int32_t max_leaf,
-          float4* d_nodes, int32_t node_cap, int32_t* d_refs, int32_t* num_nodes, std::string& err) {
+          bool extent_keys, float4* d_nodes, int32_t node_cap, int32_t* d_refs, int32_t* num_nodes, std::string& err) {
     const size_t N = (size_t)n;
     const uint32_t tri_blocks = grid_for(N).x;
     size_t sort_bytes = 0, scan_bytes = 0;
@@ -331,11 +333,19 @@ int build(Scratch& S, hipStream_t s, const float4* d_verts, int32_t nv, const in
     launches += 2;
     LB_HIP(hipGetLastError());
     uint32_t h_ctl[kCtlWords] = {};
-    LB_HIP(hipMemcpyAsync(h_ctl, ctl, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LB_HIP(hipMemcpyAsync(h_ctl, ctl, kHist * sizeof(uint32_t), hipMemcpyDeviceToHost, s));   // the flag, cmin, cmax
     LB_HIP(hipStreamSynchronize(s));
     if (h_ctl[kBad]) { err = "mesh_indices out of range"; return RT_ERR_BAD_SCENE; }
+    lbvh::KeyPlan plan = lbvh::axis_plan();
+    if (extent_keys) {   // every float decision of the plan is the host's, as in the twin
+        float cmin[3], cmax[3];
+        std::memcpy(cmin, h_ctl + kCmin, sizeof cmin);
+        std::memcpy(cmax, h_ctl + kCmax, sizeof cmax);
+        plan = lbvh::extent_plan(cmin, cmax);
+    }
 
-    hipLaunchKernelGGL(key_kernel, dim3(tri_blocks), dim3(kThreads), 0, s, (const float4*)c2, n, (const uint32_t*)ctl, keys_in);
+    hipLaunchKernelGGL(key_kernel, dim3(tri_blocks), dim3(kThreads), 0, s, (const float4*)c2, n, (const uint32_t*)ctl, plan,
+                       keys_in);
     ++launches;
     LB_HIP(rocprim::radix_sort_keys(S.sort_tmp.p, sort_bytes, keys_in, keys, N, 0u, 64u, s));
     if (n <= max_leaf) {

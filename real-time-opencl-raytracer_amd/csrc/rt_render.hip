@@ -51,6 +51,7 @@
 #include "refit.hpp"
 #include "rt_lbvh.h"
 #include "rt_scene_build.h"
+#include "rt_sah.h"
 #include "lbvh_core.hpp"
 
 #ifndef RTK_WF_WAVES
@@ -1094,6 +1095,7 @@ struct rt_ctx {
     } refit;
     rtlbvh::Scratch lbvh;                      // rt_build_bvh's buffers; no part of the scene
     rtscene::Scratch sbuild;                   // rt_build_scene's buffers; no part of the scene
+    rtlbvh::Scratch::Buf sah_part, sah_out;    // rt_scene_sah's buffers; no part of the scene
     // rt_build_scene's allocations (capacities in bytes): `built` names those of the scene it built, while
     // that scene is the context's; `spare` holds those of the scene a later call replaced, for the call
     // after it -- a mesh rebuilt again and again allocates and frees nothing
@@ -1588,6 +1590,8 @@ int rt_destroy(rt_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     rtlbvh::release(c->lbvh);
     rtscene::release(c->sbuild);
+    for (rtlbvh::Scratch::Buf* b : {&c->sah_part, &c->sah_out})
+        if (b->p) (void)hipFree(b->p);
     for (void* p : c->spare.p)
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1891,12 +1895,15 @@ int rt_last_update_timing(rt_ctx* c, float* total_ms) {
 // Both forms are synchronous.  They run on the context's stream with the context's own scratch
 // and touch nothing of the uploaded scene: frames in flight on other streams are not waited for.
 static int build_bvh(rt_ctx* c, const char* who, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx,
-                     int32_t max_leaf, rt_bvh_node* nodes, int32_t node_cap, int32_t* refs, int32_t ref_cap,
+                     int32_t max_leaf_arg, rt_bvh_node* nodes, int32_t node_cap, int32_t* refs, int32_t ref_cap,
                      int32_t* num_nodes, bool on_device, void* stream) {
     if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
     if (!verts || nv <= 0 || !idx || !nodes || !refs || !num_nodes)
         return set_err(c, std::string(who) + ": missing array", RT_ERR_INVALID_ARG);
-    if (max_leaf < 1 || max_leaf > 8) return set_err(c, std::string(who) + ": max_leaf must be 1 .. 8", RT_ERR_INVALID_ARG);
+    int32_t max_leaf = 0;
+    bool extent_keys = false;
+    if (!lbvh::split_max_leaf(max_leaf_arg, max_leaf, extent_keys))
+        return set_err(c, std::string(who) + ": max_leaf must be 1 .. 8 (| RT_BUILD_EXTENT_KEYS)", RT_ERR_INVALID_ARG);
     if (nidx <= 0 || nidx % 3 != 0 || nidx / 3 > lbvh::kMaxTris)
         return set_err(c, std::string(who) + ": needs 1 .. 2^25 triangles, 3 indices each", RT_ERR_INVALID_ARG);
     const int32_t n = nidx / 3;
@@ -1939,7 +1946,8 @@ static int build_bvh(rt_ctx* c, const char* who, const rt_float4* verts, int32_t
     HIPC(c, hipEventRecord(S.ev[0], c->stream));
     std::string err;
     int32_t nn = 0;
-    const int rc = rtlbvh::build(S, c->stream, d_verts, nv, d_idx, n, max_leaf, d_nodes, 2 * n - 1, d_refs, &nn, err);
+    const int rc = rtlbvh::build(S, c->stream, d_verts, nv, d_idx, n, max_leaf, extent_keys, d_nodes, 2 * n - 1, d_refs, &nn,
+                                 err);
     if (rc != RT_OK) {
         (void)hipStreamSynchronize(c->stream);
         return set_err(c, rc == RT_ERR_BAD_SCENE ? err : std::string(who) + ": " + err, rc);
@@ -2034,13 +2042,16 @@ static void stash_scene(rt_ctx* c) {
 }
 
 static int build_scene(rt_ctx* c, const char* who, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx,
-                       int32_t max_leaf, const rt_float4* normals, int32_t nnorm, const int32_t* normal_idx,
+                       int32_t max_leaf_arg, const rt_float4* normals, int32_t nnorm, const int32_t* normal_idx,
                        const rt_material* mats, int32_t nmat, const int32_t* tri_to_mat, bool on_device, void* stream) {
     if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
     if (!verts || !idx || !normals || !normal_idx || !mats || !tri_to_mat)
         return set_err(c, std::string(who) + ": missing array", RT_ERR_INVALID_ARG);
     if (nv <= 0 || nnorm <= 0 || nmat <= 0) return set_err(c, std::string(who) + ": empty array", RT_ERR_INVALID_ARG);
-    if (max_leaf < 1 || max_leaf > 8) return set_err(c, std::string(who) + ": max_leaf must be 1 .. 8", RT_ERR_INVALID_ARG);
+    int32_t max_leaf = 0;
+    bool extent_keys = false;
+    if (!lbvh::split_max_leaf(max_leaf_arg, max_leaf, extent_keys))
+        return set_err(c, std::string(who) + ": max_leaf must be 1 .. 8 (| RT_BUILD_EXTENT_KEYS)", RT_ERR_INVALID_ARG);
     if (nidx <= 0 || nidx % 3 != 0 || nidx / 3 > lbvh::kMaxTris)
         return set_err(c, std::string(who) + ": needs 1 .. 2^25 triangles, 3 indices each", RT_ERR_INVALID_ARG);
     const int32_t n = nidx / 3;
@@ -2113,7 +2124,8 @@ static int build_scene(rt_ctx* c, const char* who, const rt_float4* verts, int32
                                       : bad & rtscene::kBadNormals ? "mesh_normals_indices out of range"
                                                                    : "tri_to_material out of range");
     int32_t nn = 0;
-    rc = rtlbvh::build(S, c->stream, d_verts, nv, new_idx, n, max_leaf, (float4*)S.nodes.p, 2 * n - 1, new_ref_tri, &nn, err);
+    rc = rtlbvh::build(S, c->stream, d_verts, nv, new_idx, n, max_leaf, extent_keys, (float4*)S.nodes.p, 2 * n - 1, new_ref_tri,
+                       &nn, err);
     if (rc != RT_OK) return fail(rc, rc == RT_ERR_BAD_SCENE ? err : std::string(who) + ": " + err);
     const uint32_t K = (uint32_t)(nn - 1) / 2u;
     const size_t n_wnodes4 = (size_t)std::max<uint32_t>(K, 1u) * 4, n_tris4 = (size_t)n * 3 + 1, n_shade4 = (size_t)n * 7;
@@ -2222,6 +2234,56 @@ int rt_refit_level_counts(rt_ctx* c, uint32_t* counts, int32_t cap, int32_t* hei
     const int32_t h = (int32_t)r.level_begin.size() - 1;
     for (int32_t i = 0; i < h && i < cap; ++i) counts[i] = r.level_begin[i + 1] - r.level_begin[i];
     *heights = h;
+    return RT_OK;
+}
+
+// ---- the SAH cost of the scene as it stands on the GPU ----
+// Read-only and synchronous on the context's stream; frames in flight read the same records and
+// are not waited for.
+int rt_scene_sah(rt_ctx* c, double* inner_area, double* leaf_area_tris, double* root_area) {
+    if (!c || !inner_area || !leaf_area_tris || !root_area)
+        return set_err(c, "rt_scene_sah: invalid argument", RT_ERR_INVALID_ARG);
+    if (!c->have_scene) return set_err(c, "rt_scene_sah: no scene uploaded", RT_ERR_NO_SCENE);
+    auto half_area = [](const float mn[3], const float mx[3]) {
+        const float dx = mx[0] - mn[0], dy = mx[1] - mn[1], dz = mx[2] - mn[2];
+        return (double)((dx * dy + dy * dz) + dz * dx);
+    };
+    const float bmn[3] = {c->bounds_min.x, c->bounds_min.y, c->bounds_min.z};
+    const float bmx[3] = {c->bounds_max.x, c->bounds_max.y, c->bounds_max.z};
+    HIPC(c, hipSetDevice(c->device));
+    if (c->n_inner == 0) {   // the root is a leaf: its box is the scene's, its count the reference's
+        if (!c->have_bounds)
+            return set_err(c, "rt_scene_sah: a root-leaf scene from a scene image carries no box", RT_ERR_BAD_SCENE);
+        int64_t cnt = (c->root >> 26) & 31u;
+        if (!(c->root & rtk::kLeafBit)) cnt = 0;
+        if ((uint32_t)cnt == rtk::kCntEscape) {
+            const uint32_t e = c->root & 0x03FFFFFFu;
+            int2 entry = make_int2(0, 0);
+            if (e < c->n_leaf) HIPC(c, hipMemcpy(&entry, c->d_leaf + e, sizeof entry, hipMemcpyDeviceToHost));
+            cnt = std::max(entry.y, 0);
+        }
+        *root_area = half_area(bmn, bmx);
+        *inner_area = 0.0;
+        *leaf_area_tris = *root_area * (double)cnt;
+        return RT_OK;
+    }
+    const uint32_t n_inner = (uint32_t)std::min<size_t>(c->n_inner, c->n_wnodes4 / 4);   // (an image's header is not trusted)
+    const uint32_t nblocks = rtsah::blocks_for(n_inner);
+    if (rtlbvh::reserve(c->sah_part, 2 * (size_t)nblocks * sizeof(double)) != hipSuccess ||
+        rtlbvh::reserve(c->sah_out, sizeof(rtsah::Result)) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(c, "rt_scene_sah: out of device memory", RT_ERR_OUT_OF_MEMORY);
+    }
+    rtsah::Result res{};
+    HIPC(c, hipMemsetAsync(c->sah_out.p, 0, sizeof res, c->stream));
+    HIPC(c, rtsah::launch(c->d_wnodes, n_inner, c->d_leaf, (uint32_t)c->n_leaf, c->root, (double*)c->sah_part.p,
+                          (rtsah::Result*)c->sah_out.p, c->stream));
+    HIPC(c, hipMemcpyAsync(&res, c->sah_out.p, sizeof res, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, wait_stream(c->stream));
+    // rt_scene_bounds' box; a scene image carries none: the root record's own box, the union of its two slots
+    *root_area = c->have_bounds ? half_area(bmn, bmx) : half_area(res.root_box, res.root_box + 3);
+    *inner_area = *root_area + res.inner_area;
+    *leaf_area_tris = res.leaf_area_tris;
     return RT_OK;
 }
 

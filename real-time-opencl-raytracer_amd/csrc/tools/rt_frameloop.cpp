@@ -16,11 +16,12 @@
 // host builder, and the summary reports build_ms, the build's kernel time.  With --gpu-scene the whole
 // scene -- that BVH and the device records -- is built on the GPU from the mesh (rt_build_scene, no host
 // builder and no rt_upload_scene), and the summary reports scene_build_ms, the call's kernel time.
+// With --extent-keys either GPU build uses the extent-aware Morton keys (RT_BUILD_EXTENT_KEYS).
 //
 //   rt_frameloop [--dae F | --obj F | --scene cornell|knot|heightfield] [--bvh-cache F]
 //                [--width W] [--height H] [--depth D] [--frames N] [--drag DX DY]
 //                [--ppm-dir DIR] [--ppm-every K] [--device I] [--flags F] [--gpus N | --devices a,b,...]
-//                [--batch K] [--animate] [--gpu-build | --gpu-scene [--max-leaf N]]
+//                [--batch K] [--animate] [--gpu-build | --gpu-scene [--max-leaf N] [--extent-keys]]
 //
 // Prints "N.N fps" lines and a final JSON summary.
 #include <algorithm>
@@ -47,6 +48,7 @@ struct Args {
     bool gpu_build = false;     // rt_build_bvh instead of the host builder
     bool gpu_scene = false;     // rt_build_scene instead of the host builder and rt_upload_scene
     int max_leaf = 2;
+    bool extent_keys = false;   // RT_BUILD_EXTENT_KEYS for --gpu-build / --gpu-scene
 };
 
 int usage() {
@@ -55,7 +57,7 @@ int usage() {
                  "                    [--width W] [--height H] [--depth D] [--frames N] [--drag DX DY]\n"
                  "                    [--ppm-dir DIR] [--ppm-every K] [--device I] [--flags F]\n"
                  "                    [--gpus N | --devices a,b,...] [--batch K] [--animate]\n"
-                 "                    [--gpu-build | --gpu-scene [--max-leaf N]]\n");
+                 "                    [--gpu-build | --gpu-scene [--max-leaf N] [--extent-keys]]\n");
     return 2;
 }
 
@@ -81,6 +83,7 @@ bool parse(int argc, char** argv, Args& a) {
         else if (k == "--gpu-build") a.gpu_build = true;
         else if (k == "--gpu-scene") a.gpu_scene = true;
         else if (k == "--max-leaf" && need(1)) a.max_leaf = std::atoi(argv[++i]);
+        else if (k == "--extent-keys") a.extent_keys = true;
         else if (k == "--gpus" && need(1)) {
             const int n = std::atoi(argv[++i]);
             if (n < 1 || n > 64) return false;
@@ -102,7 +105,8 @@ bool parse(int argc, char** argv, Args& a) {
     return a.w > 0 && a.h > 0 && a.frames > 0 && a.depth >= 0 && a.depth <= RT_MAX_DEPTH && a.batch >= 1 &&
            a.batch <= RT_MAX_BATCH && (a.batch == 1 || a.devices.size() <= 1) &&
            (!a.animate || (a.batch == 1 && a.devices.size() <= 1)) &&   // the update is one context's
-           a.max_leaf >= 1 && a.max_leaf <= 8 && !(a.gpu_build && a.gpu_scene);
+           a.max_leaf >= 1 && a.max_leaf <= 8 && !(a.gpu_build && a.gpu_scene) &&
+           (!a.extent_keys || a.gpu_build || a.gpu_scene);
 }
 
 // Packed pixels are b<<16 | g<<8 | r (volumeRender.cl:186-195); row 0 is the first image row.
@@ -168,13 +172,14 @@ int main(int argc, char** argv) {
     std::vector<rt_bvh_node> gpu_nodes;
     std::vector<int32_t> gpu_refs;
     float build_ms = 0.0f;
+    const int32_t build_arg = a.max_leaf | (a.extent_keys ? RT_BUILD_EXTENT_KEYS : 0);
     if (a.gpu_build) {   // the BVH from the GPU: the same two arrays, into host memory
         const auto tg = clk::now();
         const int32_t ntri = mv.num_indices / 3;
         gpu_nodes.resize((size_t)std::max(2 * ntri - 1, 1));
         gpu_refs.resize((size_t)std::max(ntri, 1));
         int32_t nn = 0;
-        rc = rt_build_bvh(ctx, mv.vertices, mv.num_vertices, mv.indices, mv.num_indices, a.max_leaf, gpu_nodes.data(),
+        rc = rt_build_bvh(ctx, mv.vertices, mv.num_vertices, mv.indices, mv.num_indices, build_arg, gpu_nodes.data(),
                           (int32_t)gpu_nodes.size(), gpu_refs.data(), (int32_t)gpu_refs.size(), &nn);
         if (rc != RT_OK || rt_last_build_timing(ctx, &build_ms) != RT_OK) {
             std::fprintf(stderr, "rt_build_bvh: %s\n", rt_last_error(ctx));
@@ -189,7 +194,7 @@ int main(int argc, char** argv) {
     float scene_build_ms = 0.0f;
     if (a.gpu_scene) {   // mesh arrays in, a renderable scene out: no BVH or record ever in host memory
         const auto tg = clk::now();
-        rc = rt_build_scene(ctx, mv.vertices, mv.num_vertices, mv.indices, mv.num_indices, a.max_leaf, mv.normals,
+        rc = rt_build_scene(ctx, mv.vertices, mv.num_vertices, mv.indices, mv.num_indices, build_arg, mv.normals,
                             mv.num_normals, mv.normals_indices, mv.materials, mv.num_materials, mv.tri_to_material);
         if (rc != RT_OK || rt_last_scene_build_timing(ctx, &scene_build_ms) != RT_OK) {
             std::fprintf(stderr, "rt_build_scene: %s\n", rt_last_error(ctx));

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -35,6 +36,7 @@ RT_FLAG_WAVEFRONT = 8
 RT_FLAG_WF_SORT = 32
 RT_FLAG_STRICT_MATH = 64
 RT_MAX_DEPTH = 8
+RT_BUILD_EXTENT_KEYS = 0x100   # ORed into a builder's max_leaf: extent-aware Morton keys
 RT_MAX_BATCH = int(os.environ.get("RTAMD_MAX_BATCH", "8"))   # rt_render_device_batch frames per launch (RTAMD_MAX_BATCH: an A/B build's)
 ERRORS = {0: "RT_OK", -1: "RT_ERR_INVALID_ARG", -2: "RT_ERR_DEVICE", -3: "RT_ERR_NO_SCENE",
           -4: "RT_ERR_OUT_OF_MEMORY", -5: "RT_ERR_BAD_SCENE"}
@@ -94,7 +96,8 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_abi_version",
                "rt_refit_nodes", "rt_update_vertices", "rt_update_vertices_device", "rt_scene_bounds",
                "rt_last_update_timing", "rt_build_bvh", "rt_build_bvh_device", "rt_last_build_timing",
-               "rt_build_scene", "rt_build_scene_device", "rt_last_scene_build_timing", "rt_refit_level_counts"]
+               "rt_build_scene", "rt_build_scene_device", "rt_last_scene_build_timing", "rt_refit_level_counts",
+               "rt_scene_sah"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
                 "rt_mesh_load_dae", "rt_mesh_save_dae",
                 "rt_mesh_gen_cornell", "rt_mesh_gen_torus_knot", "rt_mesh_gen_heightfield", "rt_mesh_gen_random",
@@ -185,6 +188,7 @@ def lib() -> C.CDLL:
             "rt_build_scene_device": (C.c_int, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]),
             "rt_last_scene_build_timing": (C.c_int, [vp, C.POINTER(f32)]),
             "rt_refit_level_counts": (C.c_int, [vp, C.POINTER(u32), i32, C.POINTER(i32)]),
+            "rt_scene_sah": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
             "rt_bvh_build_lbvh": (C.c_int, [vp, i32, C.POINTER(vp)]),
             "rt_mesh_create": (vp, []),
             "rt_mesh_destroy": (None, [vp]),
@@ -308,6 +312,16 @@ def refit_nodes(scene: Scene, vertices) -> np.ndarray:
     return nodes
 
 
+SceneSah = namedtuple("SceneSah", "inner_area leaf_area_tris root_area cost")   # Renderer.scene_sah
+
+
+def _build_arg(max_leaf: int, keys: str) -> int:
+    """The builders' max_leaf argument with the key kind ORed in."""
+    if keys not in ("axis", "extent"):
+        raise ValueError(f"keys must be 'axis' or 'extent', not {keys!r}")
+    return int(max_leaf) | (RT_BUILD_EXTENT_KEYS if keys == "extent" else 0)
+
+
 class Mesh:
     """Owning wrapper of rtamd::Mesh (Mesh.h:69-101)."""
 
@@ -406,11 +420,12 @@ class Mesh:
         _check(lib().rt_bvh_build_sbvh(self._h, threads, C.byref(h)))
         return Bvh(h)
 
-    def build_lbvh(self, max_leaf: int = 2) -> "Bvh":
+    def build_lbvh(self, max_leaf: int = 2, keys: str = "axis") -> "Bvh":
         """rt_bvh_build_lbvh: the linear BVH of DESIGN.md 15 on the host -- the same bytes
-        Renderer.build_bvh builds on the GPU.  max_leaf 2 rendered C3 fastest."""
+        Renderer.build_bvh builds on the GPU.  max_leaf 2 rendered C3 fastest.
+        keys: "axis" (13 bits per axis) or "extent" (RT_BUILD_EXTENT_KEYS)."""
         h = C.c_void_p()
-        _check(lib().rt_bvh_build_lbvh(self._h, max_leaf, C.byref(h)))
+        _check(lib().rt_bvh_build_lbvh(self._h, _build_arg(max_leaf, keys), C.byref(h)))
         return Bvh(h)
 
     def load_bvh(self, path: str) -> "Bvh":
@@ -531,13 +546,15 @@ class Renderer:
         return ms.value
 
     def build_bvh(self, vertices, indices, max_leaf: int = 2, num_vertices: Optional[int] = None,
-                  num_indices: Optional[int] = None):
+                  num_indices: Optional[int] = None, keys: str = "axis"):
         """rt_build_bvh: the linear BVH of DESIGN.md 15 built on the GPU -> (nodes float32
         (nn, 12), tri_indices int32 (ntri,)), the arrays Scene and upload take.  `vertices`: float32
         (nv, 4), `indices`: int32 (3 * ntri,).  Either may instead be a (device pointer, stream)
         pair, as update_vertices accepts: the build then runs through rt_build_bvh_device (a numpy
         argument is copied to the device first), and a device array needs its count (num_vertices /
-        num_indices).  The uploaded scene is not touched."""
+        num_indices).  keys: "axis" or "extent" (RT_BUILD_EXTENT_KEYS).  The uploaded
+        scene is not touched."""
+        max_leaf = _build_arg(max_leaf, keys)
         dev_v, dev_i = isinstance(vertices, tuple), isinstance(indices, tuple)
         v = None if dev_v else np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 4)
         i = None if dev_i else np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
@@ -575,14 +592,16 @@ class Renderer:
         return ms.value
 
     def build_scene(self, scene, max_leaf: int = 2, num_vertices: Optional[int] = None,
-                    num_indices: Optional[int] = None, num_normals: Optional[int] = None) -> None:
+                    num_indices: Optional[int] = None, num_normals: Optional[int] = None, keys: str = "axis") -> None:
         """rt_build_scene: the scene of DESIGN.md 16 -- build_bvh's tree and upload's records in one
         call on the GPU.  `scene`: a Scene, a Mesh or a dict with vertices (nv, 4), indices (3 * ntri,),
         normals (nn, 4), normals_indices, materials (nm, 44) and tri_to_material (nodes / tri_indices,
         if present, are ignored).  Any of them but the materials may instead be a (device pointer,
         stream) pair, as build_bvh accepts: the call then goes through rt_build_scene_device (numpy
         arguments are copied to the device first; all pairs name one stream), and device vertices,
-        indices and normals need their counts (num_vertices / num_indices / num_normals)."""
+        indices and normals need their counts (num_vertices / num_indices / num_normals).
+        keys: "axis" or "extent" (RT_BUILD_EXTENT_KEYS)."""
+        max_leaf = _build_arg(max_leaf, keys)
         d = scene.arrays() if hasattr(scene, "arrays") else dict(scene)
         spec = [("vertices", np.float32, (-1, 4)), ("indices", np.int32, (-1,)), ("normals", np.float32, (-1, 4)),
                 ("normals_indices", np.int32, (-1,)), ("tri_to_material", np.int32, (-1,))]
@@ -636,6 +655,13 @@ class Renderer:
         _check(lib().rt_refit_level_counts(self._h, counts.ctypes.data_as(C.POINTER(C.c_uint32)), counts.size,
                                            C.byref(h)), self._h)
         return counts[:h.value]
+
+    def scene_sah(self) -> "SceneSah":
+        """rt_scene_sah: the SAH cost of the scene as it stands on the GPU ->
+        (inner_area, leaf_area_tris, root_area, cost), cost = (inner_area + leaf_area_tris) / root_area."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        _check(lib().rt_scene_sah(self._h, C.byref(a), C.byref(b), C.byref(c)), self._h)
+        return SceneSah(a.value, b.value, c.value, (a.value + b.value) / c.value if c.value else float("nan"))
 
     def scene_image_size(self) -> int:
         """Bytes of this ctx's scene image (rt_scene_image_size)."""

@@ -10,9 +10,17 @@ medians of --runs after one untimed call of each (scratch allocation):
                     hipMalloc of the new scene's arrays, the index copies, the wait for frames in
                     flight, the hipFree of the old scene -- so an upper bound of the allocation cost
 The two paths alternate run by run, so that a drift of the machine meets both.  The last scene of
-each max_leaf is checked against the parent path's scene image.  Prints one JSON line.
+each max_leaf is checked against the parent path's scene image.
 
-    python scripts/scene_build_bench.py [--config c3] [--runs 9]
+--keys names the Morton keys of the builds: axis, extent (RT_BUILD_EXTENT_KEYS,
+DESIGN.md 17) or axis,extent -- both, alternating call by call; the entries of the extent-aware keys
+carry the suffix _extent.  Every built scene also reports
+  sah               its SAH cost (rt_scene_sah), and sah_ms, the wall clock of that call
+  render_ms         the config's frame on it, kernel ms per frame (rt_last_timing), median of
+                    --frames after --warmup
+and with --sbvh the same three for an upload of the host's SBVH.  Prints one JSON line.
+
+    python scripts/scene_build_bench.py [--config c3] [--runs 9] [--keys axis] [--sbvh]
 """
 import argparse
 import ctypes as C
@@ -34,7 +42,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c3")
     ap.add_argument("--runs", type=int, default=9)
+    ap.add_argument("--frames", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=24)
+    ap.add_argument("--keys", default="axis", help="axis, extent or axis,extent (alternating)")
+    ap.add_argument("--sbvh", action="store_true", help="also rate and render the host's SBVH scene")
     a = ap.parse_args()
+    kinds = a.keys.split(",")
+    assert kinds and all(k in ("axis", "extent") for k in kinds), "--keys: axis, extent or axis,extent"
     import torch
     import rtamd
     from rtamd import configs
@@ -43,7 +57,9 @@ def main():
     m = mesh.arrays()
     v, idx = m["vertices"], m["indices"]
     n = idx.size // 3
-    out = {"config": a.config, "triangles": n, "runs": a.runs, "max_leaf": {}}
+    w, h, depth, flags = cfg["w"], cfg["h"], cfg["depth"], cfg["flags"]
+    params = mesh.camera_params(w, h)
+    out = {"config": a.config, "triangles": n, "runs": a.runs, "keys": kinds, "max_leaf": {}}
 
     ra, rb = rtamd.Renderer(0), rtamd.Renderer(0)      # A: the new call; B: the parent path
     lib = rtamd.lib()
@@ -57,15 +73,18 @@ def main():
     nn = C.c_int32()
     p = lambda t: C.c_void_p(t.data_ptr())
 
-    def scene(max_leaf):
-        rc = lib.rt_build_scene_device(ra._h, p(dev["vertices"]), v.shape[0], p(dev["indices"]), idx.size, max_leaf,
+    def arg(max_leaf, kind):
+        return max_leaf | (rtamd.RT_BUILD_EXTENT_KEYS if kind == "extent" else 0)
+
+    def scene(max_leaf, kind):
+        rc = lib.rt_build_scene_device(ra._h, p(dev["vertices"]), v.shape[0], p(dev["indices"]), idx.size, arg(max_leaf, kind),
                                        p(dev["normals"]), m["normals"].shape[0], p(dev["normals_indices"]),
                                        mats.ctypes.data_as(C.c_void_p), mats.shape[0], p(dev["tri_to_material"]),
                                        C.c_void_p(stream or None))
         assert rc == 0, lib.rt_last_error(ra._h)
 
-    def parent(max_leaf):
-        rc = lib.rt_build_bvh_device(rb._h, p(dev["vertices"]), v.shape[0], p(dev["indices"]), idx.size, max_leaf,
+    def parent(max_leaf, kind):
+        rc = lib.rt_build_bvh_device(rb._h, p(dev["vertices"]), v.shape[0], p(dev["indices"]), idx.size, arg(max_leaf, kind),
                                      p(d_nodes), 2 * n - 1, p(d_refs), n, C.byref(nn), C.c_void_p(stream or None))
         assert rc == 0, lib.rt_last_error(rb._h)
         nodes = d_nodes[:nn.value].cpu().numpy()
@@ -80,28 +99,54 @@ def main():
         r.pack_scene(buf.data_ptr(), size)
         return buf
 
-    for max_leaf in (1, 2, 4, 8):
-        scene(max_leaf)                                   # untimed: scratch allocation
-        parent(max_leaf)
-        kernel, wall, old = [], [], []
+    def rate(r):
+        """The scene of r: its SAH cost, the wall clock of the query, the config's frame on it."""
+        cost = r.scene_sah().cost
+        ts = []
         for _ in range(a.runs):
             t0 = time.perf_counter()
-            scene(max_leaf)
-            wall.append(1e3 * (time.perf_counter() - t0))
-            kernel.append(ra.last_scene_build_ms())
-            t0 = time.perf_counter()
-            parent(max_leaf)
-            old.append(1e3 * (time.perf_counter() - t0))
-        same = bool(torch.equal(image(ra), image(rb)))
-        out["max_leaf"][str(max_leaf)] = {
-            "scene_kernel_ms": round(med(kernel), 4), "scene_wall_ms": round(med(wall), 4),
-            "scene_rest_ms": round(med(w - k for w, k in zip(wall, kernel)), 4),
-            "scene_wall_min_ms": round(min(wall), 4), "scene_wall_max_ms": round(max(wall), 4),
-            "parent_wall_ms": round(med(old), 3), "parent_wall_min_ms": round(min(old), 3),
-            "parent_wall_max_ms": round(max(old), 3), "speedup": round(med(old) / med(wall), 2),
-            "inner_records": int((nn.value - 1) // 2), "heights": int(ra.refit_level_counts().size),
-            "images_equal": same}
-        assert same, f"max_leaf {max_leaf}: rt_build_scene and the parent path disagree"
+            r.scene_sah()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        r.set_params(params)
+        ms = []
+        for f in range(a.warmup + a.frames):
+            r.render(w, h, depth=depth, flags=flags)
+            if f >= a.warmup:
+                ms.append(r.last_kernel_ms())
+        return {"sah": round(cost, 3), "sah_ms": round(med(ts), 4), "render_ms": round(med(ms), 4)}
+
+    for max_leaf in (1, 2, 4, 8):
+        for kind in kinds:
+            scene(max_leaf, kind)                         # untimed: scratch allocation
+            parent(max_leaf, kind)
+        kernel, wall, old = ({k: [] for k in kinds} for _ in range(3))
+        for _ in range(a.runs):
+            for kind in kinds:                            # alternating call by call
+                t0 = time.perf_counter()
+                scene(max_leaf, kind)
+                wall[kind].append(1e3 * (time.perf_counter() - t0))
+                kernel[kind].append(ra.last_scene_build_ms())
+                t0 = time.perf_counter()
+                parent(max_leaf, kind)
+                old[kind].append(1e3 * (time.perf_counter() - t0))
+        for kind in kinds:
+            scene(max_leaf, kind)
+            parent(max_leaf, kind)
+            same = bool(torch.equal(image(ra), image(rb)))
+            k, wl, o = kernel[kind], wall[kind], old[kind]
+            out["max_leaf"][str(max_leaf) + ("_extent" if kind == "extent" else "")] = dict({
+                "scene_kernel_ms": round(med(k), 4), "scene_kernel_min_ms": round(min(k), 4),
+                "scene_kernel_max_ms": round(max(k), 4), "scene_wall_ms": round(med(wl), 4),
+                "scene_rest_ms": round(med(x - y for x, y in zip(wl, k)), 4),
+                "scene_wall_min_ms": round(min(wl), 4), "scene_wall_max_ms": round(max(wl), 4),
+                "parent_wall_ms": round(med(o), 3), "parent_wall_min_ms": round(min(o), 3),
+                "parent_wall_max_ms": round(max(o), 3), "speedup": round(med(o) / med(wl), 2),
+                "inner_records": int((nn.value - 1) // 2), "heights": int(ra.refit_level_counts().size),
+                "images_equal": same}, **rate(ra))
+            assert same, f"max_leaf {max_leaf}, {kind} keys: rt_build_scene and the parent path disagree"
+    if a.sbvh:
+        rb.upload(rtamd.Scene.from_mesh(mesh, mesh.build_sbvh(16)))
+        out["sbvh"] = rate(rb)
     ra.close()
     rb.close()
     print(json.dumps(out))
