@@ -11,13 +11,14 @@
 // hand-off between workgroups inside a kernel (the per-XCD L2s are not coherent and a CU's L1
 // is not refreshed by another CU's stores).
 #include "rt_refit.h"
+#include "rt_records.h"
 
 namespace rtrefit {
 
 namespace {
 
-constexpr uint32_t kLeafBit = 0x80000000u;   // rt_render.hip's reference encoding
-constexpr uint32_t kCntEscape = 31u;
+using rtrec::kCntEscape;
+using rtrec::kLeafBit;
 constexpr uint32_t kThreads = 256;
 constexpr uint32_t kTopMax = 1024;           // heights with at most this many records run in the top kernel
 
@@ -83,7 +84,7 @@ __device__ __forceinline__ void child_box(const DevArgs& A, uint32_t ref, int sl
         }
         return;
     }
-    int32_t cnt = (int32_t)((ref >> 26) & 31u), off = (int32_t)(ref & 0x03FFFFFFu);
+    int32_t cnt = (int32_t)rtrec::ref_count(ref), off = (int32_t)rtrec::ref_offset(ref);
     if ((uint32_t)cnt == kCntEscape) {
         const int2 e = A.leaf_table[off];
         off = e.x;

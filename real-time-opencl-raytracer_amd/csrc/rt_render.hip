@@ -34,6 +34,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -44,11 +45,14 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "rt_abi.h"
+#include "rt_records.h"
 #include "rt_refit.h"
 #include "refit.hpp"
+#include "scene_encode.hpp"
 #include "rt_lbvh.h"
 #include "rt_scene_build.h"
 #include "rt_sah.h"
@@ -99,9 +103,9 @@ namespace rtk {
 
 constexpr int kStackSize = 65;                       // volumeRender.cl:636
 constexpr float kTmin = 0.001f;                      // volumeRender.cl:640
-constexpr uint32_t kLeafBit = 0x80000000u;
-constexpr uint32_t kRefError = 0x7FFFFFFFu;          // popped -> traversal returns -1
-constexpr uint32_t kCntEscape = 31u;
+using rtrec::kCntEscape;
+using rtrec::kLeafBit;
+using rtrec::kRefError;
 constexpr int kLdsStack = RTK_LDS_STACK;
 constexpr int kGlobalStack = 64 - kLdsStack;         // slots kLdsStack..63
 constexpr uint32_t kBlockPx = 16;                    // a block = 2 x 2 tiles of 8 x 8 pixels
@@ -238,13 +242,13 @@ struct BatchCams {
 };
 
 __device__ __forceinline__ void leaf_range(const DevScene& S, uint32_t ref, int& off, int& cnt) {
-    uint32_t c = (ref >> 26) & 31u;
+    uint32_t c = rtrec::ref_count(ref);
     if (c == kCntEscape) {
-        int2 e = S.leaf_table[ref & 0x03FFFFFFu];
+        int2 e = S.leaf_table[rtrec::ref_offset(ref)];
         off = e.x;
         cnt = e.y;
     } else {
-        off = (int)(ref & 0x03FFFFFFu);
+        off = (int)rtrec::ref_offset(ref);
         cnt = (int)c;
     }
 }
@@ -991,6 +995,53 @@ __global__ void __launch_bounds__(256) frame_checksum_kernel(const uint32_t* __r
 // Host side: context, upload/repack, launch.
 // ============================================================================
 
+// A scene on the device and everything it owns.  `own` is the only place that holds
+// an owning pointer of a scene array: the accessors return views, and nothing stores one.
+struct Scene {
+    enum { kRec, kTris, kShade, kLeaf, kIdx, kNormalIdx, kRefTri, kLevelIds, kLevelBegin, kOut, kVerts, kNormals, kCount };
+    struct Owned {   // one allocation per kind, capacities in bytes; a move leaves the source empty, and there are no copies
+        std::array<void*, kCount> p{};
+        std::array<size_t, kCount> cap{};
+        Owned() = default;
+        Owned(Owned&& o) noexcept { *this = std::move(o); }
+        Owned& operator=(Owned&& o) noexcept { p = std::exchange(o.p, {}); cap = std::exchange(o.cap, {}); return *this; }
+    } own;
+    bool pooled = false;          // rt_build_scene's allocations: released into the spare pool, not freed
+    // records: kRec holds the inner records and, unless `split`, the triangle records right after them
+    size_t n_wnodes4 = 0, n_tris4 = 0, n_shade4 = 0, n_leaf = 0;   // element counts of the scene arrays
+    uint32_t root = 0, n_inner = 0;
+    int fast_div = 0, clean = 0;
+    bool split = false;           // records >= 2 GiB: two allocations (kRec, kTris), general traversal only
+    bool have_bounds = false;     // rt_scene_bounds: the uploaded / built / refit root box
+    rt_float4 bounds_min{}, bounds_max{};
+    // Animated geometry (rt_update_vertices): a refittable scene keeps per-triangle vertex / normal
+    // indices, the triangle of every reference record, the refit plan's level lists and
+    // rtrefit::DevArgs::out (kIdx .. kOut), and the staging of the host form's arrays (kVerts,
+    // kNormals: allocated on first use unless rt_build_scene brought them)
+    bool refittable = false;
+    std::string why = "no scene uploaded";   // why the scene has no refit data
+    int32_t nv = 0, nnorm = 0;
+    uint32_t nref = 0, ntri = 0;
+    std::vector<uint32_t> level_begin;       // host copy: heights + 1 entries
+
+    float4* wnodes() const { return (float4*)own.p[kRec]; }
+    float4* tris() const { return split ? (float4*)own.p[kTris] : wnodes() + n_wnodes4; }
+    float4* shade() const { return (float4*)own.p[kShade]; }
+    int2* leaf() const { return (int2*)own.p[kLeaf]; }
+    int32_t* idx() const { return (int32_t*)own.p[kIdx]; }
+    int32_t* normal_idx() const { return (int32_t*)own.p[kNormalIdx]; }
+    int32_t* ref_tri() const { return (int32_t*)own.p[kRefTri]; }
+    uint32_t* level_ids() const { return (uint32_t*)own.p[kLevelIds]; }
+    uint32_t* d_level_begin() const { return (uint32_t*)own.p[kLevelBegin]; }
+    uint32_t* out() const { return (uint32_t*)own.p[kOut]; }
+    float4* verts() const { return (float4*)own.p[kVerts]; }
+    float4* normals() const { return (float4*)own.p[kNormals]; }
+    // what a frame reads, in the scene image's order: {array, bytes}
+    std::array<std::pair<void*, size_t>, 4> sections() const {
+        return {{{wnodes(), n_wnodes4 * 16}, {tris(), n_tris4 * 16}, {shade(), n_shade4 * 16}, {leaf(), n_leaf * 8}}};
+    }
+};
+
 struct rt_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -1002,17 +1053,11 @@ struct rt_ctx {
     static constexpr int kRing = 64;
     FrameEv ring[kRing];
     uint64_t frames = 0;
-    float4* d_wnodes = nullptr;
-    float4* d_tris = nullptr;
-    float4* d_shade = nullptr;
-    int2* d_leaf = nullptr;
-    size_t n_wnodes4 = 0, n_tris4 = 0, n_shade4 = 0, n_leaf = 0;   // element counts of the scene arrays
-    uint32_t root = 0;
-    uint32_t n_inner = 0;
-    int fast_div = 0;
-    int clean = 0;
-    bool split_records = false;   // records >= 2 GiB: two allocations, general traversal only
+    Scene scene;                  // replaced by install_scene alone
     bool have_scene = false;
+    // rt_build_scene's allocations of the scene a later call replaced, at most one per kind, for the
+    // build after it: a mesh rebuilt again and again allocates and frees nothing
+    Scene::Owned spare;
     bool have_params = false;
     rt_params params{};
     uint32_t* d_out = nullptr; size_t out_cap = 0;
@@ -1072,23 +1117,8 @@ struct rt_ctx {
     hipEvent_t gstart = nullptr;
     std::vector<FrameSlot*> last_group;   // the slots of the last grouped rt_render
     bool timing_valid = false;
-    // Animated geometry (rt_update_vertices): what a refittable scene keeps on the
-    // device besides its records -- per-triangle vertex / normal indices, the triangle of every
-    // reference record and the refit plan's level lists -- and the update's own buffers.
+    // rt_update_vertices' own state (the scene's refit data is the Scene's)
     struct Refit {
-        bool have = false;
-        std::string why;                       // why the scene has no refit data
-        int32_t nv = 0, nnorm = 0;
-        uint32_t nref = 0, ntri = 0;
-        int32_t* d_idx = nullptr;
-        int32_t* d_normal_idx = nullptr;
-        int32_t* d_ref_tri = nullptr;
-        uint32_t* d_level_ids = nullptr;
-        uint32_t* d_level_begin = nullptr;
-        uint32_t* d_out = nullptr;             // rtrefit::DevArgs::out
-        float4* d_verts = nullptr;             // staging of the host form's arrays
-        float4* d_normals = nullptr;
-        std::vector<uint32_t> level_begin;     // host copy: heights + 1 entries
         hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // around the update's kernels; the caller's stream
         bool timed = false;
         uint32_t launches = 0;
@@ -1096,17 +1126,6 @@ struct rt_ctx {
     rtlbvh::Scratch lbvh;                      // rt_build_bvh's buffers; no part of the scene
     rtscene::Scratch sbuild;                   // rt_build_scene's buffers; no part of the scene
     rtlbvh::Scratch::Buf sah_part, sah_out;    // rt_scene_sah's buffers; no part of the scene
-    // rt_build_scene's allocations (capacities in bytes): `built` names those of the scene it built, while
-    // that scene is the context's; `spare` holds those of the scene a later call replaced, for the call
-    // after it -- a mesh rebuilt again and again allocates and frees nothing
-    struct SceneArrays {
-        enum { kRec, kTris, kShade, kLeaf, kIdx, kNormalIdx, kRefTri, kLevelIds, kLevelBegin, kOut, kVerts, kNormals, kCount };
-        void* p[kCount] = {};
-        size_t cap[kCount] = {};
-    };
-    SceneArrays built, spare;
-    bool have_bounds = false;                 // rt_scene_bounds: the uploaded / refit root box
-    rt_float4 bounds_min{}, bounds_max{};
     std::string err;
 };
 
@@ -1242,48 +1261,72 @@ static uint64_t record_limit() {
 
 static bool records_split(size_t n_wnodes4, size_t n_tris4) { return (n_wnodes4 + n_tris4) * 16 >= record_limit(); }
 
-static hipError_t alloc_records(rt_ctx* c, size_t n_wnodes4, size_t n_tris4) {
-    c->split_records = records_split(n_wnodes4, n_tris4);
-    if (c->split_records) {
-        hipError_t e = hipMalloc((void**)&c->d_wnodes, n_wnodes4 * sizeof(float4));
-        if (e != hipSuccess) { c->d_wnodes = nullptr; return e; }
-        e = hipMalloc((void**)&c->d_tris, n_tris4 * sizeof(float4));
-        if (e != hipSuccess) c->d_tris = nullptr;
-        return e;
+// One array of a scene: from the pool where its allocation of that kind is large enough, else fresh.
+static hipError_t scene_alloc(Scene& s, int k, size_t bytes, Scene::Owned* pool) {
+    bytes = std::max<size_t>(bytes, 16);
+    if (pool && pool->p[k] && pool->cap[k] >= bytes) {
+        s.own.p[k] = pool->p[k]; s.own.cap[k] = pool->cap[k];
+        pool->p[k] = nullptr; pool->cap[k] = 0;
+        return hipSuccess;
     }
-    float4* p = nullptr;
-    const hipError_t e = hipMalloc((void**)&p, (n_wnodes4 + n_tris4) * sizeof(float4));
-    if (e != hipSuccess) return e;
-    c->d_wnodes = p;
-    c->d_tris = p + n_wnodes4;
-    return hipSuccess;
+    const hipError_t e = hipMalloc(&s.own.p[k], bytes);
+    if (e != hipSuccess) s.own.p[k] = nullptr; else s.own.cap[k] = bytes;
+    return e;
 }
 
-// a context without refit data (the events stay: rt_destroy)
-static void free_refit(rt_ctx* c, const char* why) {
-    rt_ctx::Refit& r = c->refit;
-    for (void* p : {(void*)r.d_idx, (void*)r.d_normal_idx, (void*)r.d_ref_tri, (void*)r.d_level_ids,
-                    (void*)r.d_level_begin, (void*)r.d_out, (void*)r.d_verts, (void*)r.d_normals})
-        if (p) (void)hipFree(p);
-    r.d_idx = r.d_normal_idx = r.d_ref_tri = nullptr;
-    r.d_level_ids = r.d_level_begin = r.d_out = nullptr;
-    r.d_verts = r.d_normals = nullptr;
-    r.level_begin.clear();
-    r.have = false;
-    r.timed = false;
-    r.why = why;
+// What a frame reads, with its counts: the inner and triangle records in one allocation or two
+// (records_split), the shading records and the escape leaves.
+static hipError_t scene_alloc_records(Scene& s, size_t n_wnodes4, size_t n_tris4, size_t n_shade4, size_t n_leaf,
+                                      Scene::Owned* pool) {
+    s.n_wnodes4 = n_wnodes4; s.n_tris4 = n_tris4; s.n_shade4 = n_shade4; s.n_leaf = n_leaf;
+    s.split = records_split(n_wnodes4, n_tris4);
+    hipError_t e = scene_alloc(s, Scene::kRec, (s.split ? n_wnodes4 : n_wnodes4 + n_tris4) * sizeof(float4), pool);
+    if (e == hipSuccess && s.split) e = scene_alloc(s, Scene::kTris, n_tris4 * sizeof(float4), pool);
+    if (e == hipSuccess) e = scene_alloc(s, Scene::kShade, n_shade4 * sizeof(float4), pool);
+    return e == hipSuccess ? scene_alloc(s, Scene::kLeaf, n_leaf * sizeof(int2), pool) : e;
 }
 
-static void free_scene(rt_ctx* c) {
-    c->built = rt_ctx::SceneArrays{};
-    free_refit(c, "no scene uploaded");
-    c->have_bounds = false;
-    if (c->split_records && c->d_tris) (void)hipFree(c->d_tris);
-    if (c->d_wnodes) (void)hipFree(c->d_wnodes);   // (one block: inner records, then triangle records)
-    if (c->d_shade) (void)hipFree(c->d_shade);
-    if (c->d_leaf) (void)hipFree(c->d_leaf);
-    c->d_wnodes = nullptr; c->d_tris = nullptr; c->d_shade = nullptr; c->d_leaf = nullptr;
+// Every owned array from kind `first` on goes to the pool (which keeps the larger allocation of
+// a kind) or, without one, is freed; with first = 0 the scene is then empty.  Idempotent.
+static void scene_release(Scene& s, Scene::Owned* pool, int first = 0) {
+    for (int k = first; k < Scene::kCount; ++k) {
+        if (!s.own.p[k]) continue;
+        if (pool && pool->cap[k] < s.own.cap[k]) {
+            std::swap(pool->p[k], s.own.p[k]);
+            std::swap(pool->cap[k], s.own.cap[k]);
+        }
+        if (s.own.p[k]) (void)hipFree(s.own.p[k]);
+        s.own.p[k] = nullptr; s.own.cap[k] = 0;
+    }
+    if (first == 0) s = Scene{};
+}
+
+// A producer's scene until install_scene takes it: released on every other way out.
+struct PendingScene {
+    Scene s;
+    Scene::Owned* pool;   // where its arrays come from and go back to (rt_build_scene), or NULL
+    explicit PendingScene(Scene::Owned* from) : pool(from) { s.pooled = from != nullptr; }
+    ~PendingScene() { scene_release(s, pool); }
+};
+
+// The context without a scene, after waiting for the frames in flight, which still read it.  The
+// arrays rt_build_scene made go to the spare pool, any others are freed.
+static int drop_scene(rt_ctx* c) {
+    for (auto& f : c->slots)
+        if (f.idle) HIPC(c, hipEventSynchronize(f.idle));
+    scene_release(c->scene, c->scene.pooled ? &c->spare : nullptr);
     c->have_scene = false;
+    c->refit.timed = false;
+    return RT_OK;
+}
+
+// The single place that replaces the context's scene.
+static int install_scene(rt_ctx* c, Scene&& s) {
+    if (const int rc = drop_scene(c)) return rc;
+    c->scene = std::move(s);
+    c->have_scene = true;
+    ++c->scene_gen;
+    return RT_OK;
 }
 
 // Static block -> tile order (the first frame of a geometry, and RT_FLAG_STATIC_ORDER).
@@ -1568,7 +1611,7 @@ int rt_destroy(rt_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& f : c->slots)
         if (f.idle) (void)hipEventSynchronize(f.idle);   // frames may still run on caller streams
-    free_scene(c);
+    scene_release(c->scene, nullptr);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->d_hits) (void)hipFree(c->d_hits);
     if (c->d_t) (void)hipFree(c->d_t);
@@ -1607,207 +1650,52 @@ int rt_upload_scene(rt_ctx* c, const rt_float4* verts, int32_t nv, const int32_t
     if (!verts || nv <= 0 || !idx || nidx <= 0 || nidx % 3 || !nodes || nn <= 0 || !refs || nref < 0 || !normals ||
         nnorm <= 0 || !normal_idx || !mats || nmat <= 0 || !tri_to_mat)
         return set_err(c, "rt_upload_scene: missing or empty array", RT_ERR_INVALID_ARG);
-    const int32_t ntri = nidx / 3;
-    for (int32_t i = 0; i < nidx; ++i) {
-        if (idx[i] < 0 || idx[i] >= nv) return set_err(c, "mesh_indices out of range", RT_ERR_BAD_SCENE);
-        if (normal_idx[i] < 0 || normal_idx[i] >= nnorm) return set_err(c, "mesh_normals_indices out of range", RT_ERR_BAD_SCENE);
-    }
-    for (int32_t t = 0; t < ntri; ++t)
-        if (tri_to_mat[t] < 0 || tri_to_mat[t] >= nmat) return set_err(c, "tri_to_material out of range", RT_ERR_BAD_SCENE);
-    for (int32_t i = 0; i < nref; ++i)
-        if (refs[i] < 0 || refs[i] % 3 != 0 || refs[i] + 2 >= nidx)
-            return set_err(c, "bvh_tris_indices entry out of range", RT_ERR_BAD_SCENE);
-
-    // --- reference encoding of every node (traverse_bvh semantics, volumeRender.cl:829-856) ---
-    std::vector<int32_t> inner_id(nn, -1);
-    std::vector<int2> leaf_table;
-    std::vector<uint32_t> ref_of(nn, 0);
-    // inner ids in pre-order of reachability from the root; detect cycles (the
-    // reference would spin forever on some of them).
-    std::vector<uint8_t> state(nn, 0);  // 0 new, 1 on path, 2 done
-    {
-        std::vector<std::pair<int32_t, int>> stk;
-        int32_t next = 0;
-        stk.push_back({0, 0});
-        while (!stk.empty()) {
-            auto& top = stk.back();
-            const int32_t n = top.first;
-            const rt_bvh_node& nd = nodes[n];
-            if (top.second == 0) {
-                if (state[n] == 2) { stk.pop_back(); continue; }
-                if (state[n] == 1) return set_err(c, "BVH has a cycle", RT_ERR_BAD_SCENE);
-                state[n] = 1;
-                bool valid_inner = nd.offset_left >= 0 && nd.offset_right >= 0 && nd.offset_left < nn && nd.offset_right < nn;
-                if (nd.offset_left >= 0 && valid_inner) inner_id[n] = next++;
-            }
-            const bool is_inner = nd.offset_left >= 0 && inner_id[n] >= 0;
-            if (is_inner && top.second < 2) {
-                int32_t child = top.second == 0 ? nd.offset_left : nd.offset_right;
-                top.second++;
-                if (state[child] == 1) return set_err(c, "BVH has a cycle", RT_ERR_BAD_SCENE);
-                if (state[child] == 0) stk.push_back({child, 0});
-                continue;
-            }
-            state[n] = 2;
-            stk.pop_back();
-        }
-        // the first kBfsTop inner nodes in breadth-first order from the root get ids
-        // 0..kBfsTop-1 (the top of the tree, which every ray walks, in 64 KB); the rest
-        // keep their pre-order
-        constexpr int32_t kBfsTop = 1024;
-        std::vector<int32_t> bfs;
-        std::vector<uint8_t> seen(nn, 0);
-        if (inner_id[0] >= 0) { bfs.push_back(0); seen[0] = 1; }
-        for (size_t i = 0; i < bfs.size() && (int32_t)bfs.size() < kBfsTop; ++i) {
-            const rt_bvh_node& nd = nodes[bfs[i]];
-            for (int32_t ch : {nd.offset_left, nd.offset_right})
-                if (inner_id[ch] >= 0 && !seen[ch] && (int32_t)bfs.size() < kBfsTop) {
-                    seen[ch] = 1;
-                    bfs.push_back(ch);
-                }
-        }
-        std::vector<int32_t> by_old(next, -1);
-        for (int32_t n = 0; n < nn; ++n)
-            if (inner_id[n] >= 0) by_old[inner_id[n]] = n;
-        int32_t id = 0;
-        for (int32_t n : bfs) inner_id[n] = id++;
-        for (int32_t o = 0; o < next; ++o)
-            if (!seen[by_old[o]]) inner_id[by_old[o]] = id++;
-    }
-    bool clean = true;
-    for (int32_t n = 0; n < nn; ++n)
-        if (state[n] != 0 && nodes[n].offset_left >= 0 && inner_id[n] < 0) clean = false;
-    int32_t n_inner = 0;
-    for (int32_t n = 0; n < nn; ++n) {
-        const rt_bvh_node& nd = nodes[n];
-        if (inner_id[n] >= 0) ++n_inner;
-        if (nd.offset_left >= 0) {
-            ref_of[n] = inner_id[n] >= 0 ? (uint32_t)inner_id[n] : rtk::kRefError;
-        } else {
-            int32_t off = nd.offset_tris, cnt = nd.num_tris < 0 ? 0 : nd.num_tris;
-            if (cnt > 0 && (off < 0 || (int64_t)off + cnt > nref))
-                return set_err(c, "leaf triangle range out of bounds", RT_ERR_BAD_SCENE);
-            if (cnt == 0) off = 0;
-            if (cnt < (int32_t)rtk::kCntEscape && off < (1 << 26)) {
-                ref_of[n] = rtk::kLeafBit | ((uint32_t)cnt << 26) | (uint32_t)off;
-            } else {
-                if (leaf_table.size() >= (1u << 26)) return set_err(c, "too many escape leaves", RT_ERR_BAD_SCENE);
-                ref_of[n] = rtk::kLeafBit | (rtk::kCntEscape << 26) | (uint32_t)leaf_table.size();
-                leaf_table.push_back(make_int2(off, cnt));
-            }
-        }
-    }
-    std::vector<float4> wn((size_t)std::max(n_inner, 1) * 4, make_float4(0, 0, 0, 0));
-    bool fast_ok = true;  // slab-test fast quotient domain (rt_kernel_body.inc axis_ok)
-    for (int32_t n = 0; n < nn; ++n) {
-        if (inner_id[n] < 0) continue;
-        const rt_bvh_node& L = nodes[nodes[n].offset_left];
-        const rt_bvh_node& R = nodes[nodes[n].offset_right];
-        float4* q = &wn[(size_t)inner_id[n] * 4];
-        // axis-major: {L.min, R.min, L.max, R.max} per axis (rt_kernel_body.inc slab2_pk)
-        q[0] = make_float4(L.min.x, R.min.x, L.max.x, R.max.x);
-        q[1] = make_float4(L.min.y, R.min.y, L.max.y, R.max.y);
-        q[2] = make_float4(L.min.z, R.min.z, L.max.z, R.max.z);
-        uint32_t r0 = ref_of[nodes[n].offset_left], r1 = ref_of[nodes[n].offset_right];
-        float f0, f1;
-        std::memcpy(&f0, &r0, 4);
-        std::memcpy(&f1, &r1, 4);
-        q[3] = make_float4(f0, f1, 0.0f, 0.0f);
-        for (int k = 0; k < 3; ++k) {
-            const float* qf = &q[k].x;
-            for (int j = 0; j < 4; ++j) {
-                const float a = std::fabs(qf[j]);
-                if (!(a == 0.0f || (a >= 0x1p-66f && a <= 0x1p60f))) fast_ok = false;
-            }
-        }
-    }
-    // triangle reference records {v0|id, e1, e2} (volumeRender.cl:965-974), layout of tri_rec
-    std::vector<float4> tr((size_t)std::max(nref, 1) * 3 + 1, make_float4(0, 0, 0, 0));
-    for (int32_t i = 0; i < nref; ++i) {
-        const int32_t tri1 = refs[i];
-        const rt_float4 v0 = verts[idx[tri1]], v1 = verts[idx[tri1 + 1]], v2 = verts[idx[tri1 + 2]];
-        float idf;
-        std::memcpy(&idf, &tri1, 4);
-        tr[(size_t)i * 3 + 0] = make_float4(v0.x, v0.y, v0.z, idf);
-        tr[(size_t)i * 3 + 1] = make_float4(v1.x - v0.x, v1.y - v0.y, v1.z - v0.z, 0.0f);
-        tr[(size_t)i * 3 + 2] = make_float4(v2.x - v0.x, v2.y - v0.y, v2.z - v0.z, 0.0f);
-    }
-    // per-triangle shading records (volumeRender.cl:1306-1374)
-    std::vector<float4> sh((size_t)ntri * 7);
-    for (int32_t t = 0; t < ntri; ++t) {
-        float4* s = &sh[(size_t)t * 7];
-        for (int k = 0; k < 3; ++k) {
-            const rt_float4 v = verts[idx[3 * t + k]];
-            const rt_float4 n = normals[normal_idx[3 * t + k]];
-            s[k] = make_float4(v.x, v.y, v.z, 0.0f);
-            s[3 + k] = make_float4(n.x, n.y, n.z, 0.0f);
-        }
-        const rt_float4 d = mats[tri_to_mat[t]].diffuse;
-        s[6] = make_float4(d.x, d.y, d.z, 0.0f);
-    }
-    if (leaf_table.empty()) leaf_table.push_back(make_int2(0, 0));
+    rtamd::EncodedScene enc;
+    static_assert(sizeof(rt_float4) == sizeof(float4) && sizeof(enc.leaf_table[0]) == sizeof(int2), "the encoded layouts");
+    std::string why;
+    if (const int rc = rtamd::encode_scene(verts, nv, idx, nidx, nodes, nn, refs, nref, normals, nnorm, normal_idx, mats, nmat,
+                                           tri_to_mat, enc, why))
+        return set_err(c, why, rc);
 
     HIPC(c, hipSetDevice(c->device));
-    for (auto& f : c->slots)
-        if (f.idle) HIPC(c, hipEventSynchronize(f.idle));   // frames in flight still read the old scene
-    free_scene(c);
-    HIPC(c, alloc_records(c, wn.size(), tr.size()));
-    HIPC(c, hipMalloc((void**)&c->d_shade, sh.size() * sizeof(float4)));
-    HIPC(c, hipMalloc((void**)&c->d_leaf, leaf_table.size() * sizeof(int2)));
-    HIPC(c, hipMemcpy(c->d_wnodes, wn.data(), wn.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->d_tris, tr.data(), tr.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->d_shade, sh.data(), sh.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIPC(c, hipMemcpy(c->d_leaf, leaf_table.data(), leaf_table.size() * sizeof(int2), hipMemcpyHostToDevice));
-    c->n_wnodes4 = wn.size();
-    c->n_tris4 = tr.size();
-    c->n_shade4 = sh.size();
-    c->n_leaf = leaf_table.size();
-    c->root = ref_of[0];
-    c->n_inner = (uint32_t)n_inner;
-    c->fast_div = fast_ok ? 1 : 0;
-    c->clean = clean ? 1 : 0;
-    c->have_scene = true;
-    ++c->scene_gen;
-    c->bounds_min = nodes[0].min;
-    c->bounds_max = nodes[0].max;
-    c->have_bounds = true;
+    if (const int rc = drop_scene(c)) return rc;   // before the new one is allocated: peak memory is one scene's
+    PendingScene ps(nullptr);
+    Scene& S = ps.s;
+    HIPC(c, scene_alloc_records(S, enc.wnodes.size(), enc.tris.size(), enc.shade.size(), enc.leaf_table.size(), nullptr));
+    HIPC(c, hipMemcpy(S.wnodes(), enc.wnodes.data(), S.n_wnodes4 * sizeof(float4), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(S.tris(), enc.tris.data(), S.n_tris4 * sizeof(float4), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(S.shade(), enc.shade.data(), S.n_shade4 * sizeof(float4), hipMemcpyHostToDevice));
+    HIPC(c, hipMemcpy(S.leaf(), enc.leaf_table.data(), S.n_leaf * sizeof(int2), hipMemcpyHostToDevice));
+    S.root = enc.root; S.n_inner = enc.n_inner; S.fast_div = enc.fast_div; S.clean = enc.clean;
+    S.bounds_min = nodes[0].min; S.bounds_max = nodes[0].max; S.have_bounds = true;
     // refit data (rt_update_vertices): only a refittable scene gets it; any other renders as ever
     rtrefit::Plan plan;
-    std::string why;
-    if (rtrefit::plan_build(nodes, nn, nref, inner_id.data(), plan, why) != RT_OK) {
-        c->refit.why = why;
-        return RT_OK;
+    if (rtrefit::plan_build(nodes, nn, nref, enc.inner_id.data(), plan, S.why) != RT_OK) return install_scene(c, std::move(S));
+    if (plan.ids.size() != (size_t)S.n_inner) {   // (a refittable scene is clean: every inner node has a record)
+        S.why = "refit: the plan does not cover the inner records";
+        return install_scene(c, std::move(S));
     }
-    if (plan.ids.size() != (size_t)n_inner) {   // (a refittable scene is clean: every inner node has a record)
-        c->refit.why = "refit: the plan does not cover the inner records";
-        return RT_OK;
-    }
-    rt_ctx::Refit& r = c->refit;
-    const uint32_t out0[8] = {(uint32_t)c->fast_div, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    float box[8];
-    std::memcpy(box, out0, sizeof box);
-    box[2] = nodes[0].min.x; box[3] = nodes[0].min.y; box[4] = nodes[0].min.z;
-    box[5] = nodes[0].max.x; box[6] = nodes[0].max.y; box[7] = nodes[0].max.z;
-    auto put = [&](auto*& d, const void* src, size_t bytes) {
-        hipError_t e = hipMalloc((void**)&d, std::max<size_t>(bytes, 16));
-        if (e == hipSuccess && bytes) e = hipMemcpy(d, src, bytes, hipMemcpyHostToDevice);
+    uint32_t out0[8] = {(uint32_t)S.fast_div, 0u, 0u, 0u, 0u, 0u, 0u, 0u};   // rtrefit::DevArgs::out: the flag, then the root box
+    std::memcpy(out0 + 2, &nodes[0].min, 12);
+    std::memcpy(out0 + 5, &nodes[0].max, 12);
+    auto put = [&](int k, const void* src, size_t bytes) {
+        hipError_t e = scene_alloc(S, k, bytes, nullptr);
+        if (e == hipSuccess && bytes) e = hipMemcpy(S.own.p[k], src, bytes, hipMemcpyHostToDevice);
         return e == hipSuccess;
     };
-    if (!put(r.d_idx, idx, (size_t)nidx * 4) || !put(r.d_normal_idx, normal_idx, (size_t)nidx * 4) ||
-        !put(r.d_ref_tri, refs, (size_t)nref * 4) || !put(r.d_level_ids, plan.ids.data(), plan.ids.size() * 4) ||
-        !put(r.d_level_begin, plan.level_begin.data(), plan.level_begin.size() * 4) || !put(r.d_out, box, sizeof box)) {
+    if (!put(Scene::kIdx, idx, (size_t)nidx * 4) || !put(Scene::kNormalIdx, normal_idx, (size_t)nidx * 4) ||
+        !put(Scene::kRefTri, refs, (size_t)nref * 4) || !put(Scene::kLevelIds, plan.ids.data(), plan.ids.size() * 4) ||
+        !put(Scene::kLevelBegin, plan.level_begin.data(), plan.level_begin.size() * 4) || !put(Scene::kOut, out0, sizeof out0)) {
         (void)hipGetLastError();
-        free_refit(c, "refit: out of device memory for the refit data");
-        return RT_OK;
+        scene_release(S, nullptr, Scene::kIdx);   // the records stay: the scene renders, without refit data
+        S.why = "refit: out of device memory for the refit data";
+        return install_scene(c, std::move(S));
     }
-    r.level_begin = plan.level_begin;
-    r.nv = nv;
-    r.nnorm = nnorm;
-    r.nref = (uint32_t)nref;
-    r.ntri = (uint32_t)ntri;
-    r.why.clear();
-    r.have = true;
-    return RT_OK;
+    S.level_begin = plan.level_begin;
+    S.nv = nv; S.nnorm = nnorm; S.nref = (uint32_t)nref; S.ntri = (uint32_t)(nidx / 3);
+    S.why.clear();
+    S.refittable = true;
+    return install_scene(c, std::move(S));
 }
 
 // ---- animated geometry: vertex updates with an on-GPU refit ----
@@ -1820,10 +1708,11 @@ static int update_vertices(rt_ctx* c, const char* who, const rt_float4* verts, i
     if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
     if (!c->have_scene) return set_err(c, std::string(who) + ": no scene uploaded", RT_ERR_NO_SCENE);
     rt_ctx::Refit& r = c->refit;
-    if (!r.have) return set_err(c, std::string(who) + ": the scene has no refit data (" + r.why + ")", RT_ERR_BAD_SCENE);
-    if (!verts || nv != r.nv || (normals && nnorm != r.nnorm))
-        return set_err(c, std::string(who) + ": vertices / normals must be the upload's counts (" + std::to_string(r.nv) +
-                              ", " + std::to_string(r.nnorm) + ")", RT_ERR_INVALID_ARG);
+    Scene& S = c->scene;
+    if (!S.refittable) return set_err(c, std::string(who) + ": the scene has no refit data (" + S.why + ")", RT_ERR_BAD_SCENE);
+    if (!verts || nv != S.nv || (normals && nnorm != S.nnorm))
+        return set_err(c, std::string(who) + ": vertices / normals must be the upload's counts (" + std::to_string(S.nv) +
+                              ", " + std::to_string(S.nnorm) + ")", RT_ERR_INVALID_ARG);
     HIPC(c, hipSetDevice(c->device));
     for (hipEvent_t& e : r.ev)
         if (!e) HIPC(c, hipEventCreate(&e));
@@ -1835,33 +1724,34 @@ static int update_vertices(rt_ctx* c, const char* who, const rt_float4* verts, i
         HIPC(c, hipEventRecord(r.ev[2], (hipStream_t)stream));
         HIPC(c, hipStreamWaitEvent(c->stream, r.ev[2], 0));
     } else {
-        if (!r.d_verts) HIPC(c, hipMalloc((void**)&r.d_verts, (size_t)r.nv * sizeof(float4)));
-        HIPC(c, hipMemcpyAsync(r.d_verts, verts, (size_t)r.nv * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        d_verts = r.d_verts;
+        Scene::Owned* pool = S.pooled ? &c->spare : nullptr;   // the staging is the scene's, like its other arrays
+        if (!S.verts()) HIPC(c, scene_alloc(S, Scene::kVerts, (size_t)S.nv * sizeof(float4), pool));
+        HIPC(c, hipMemcpyAsync(S.verts(), verts, (size_t)S.nv * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+        d_verts = S.verts();
         if (normals) {
-            if (!r.d_normals) HIPC(c, hipMalloc((void**)&r.d_normals, (size_t)r.nnorm * sizeof(float4)));
-            HIPC(c, hipMemcpyAsync(r.d_normals, normals, (size_t)r.nnorm * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-            d_normals = r.d_normals;
+            if (!S.normals()) HIPC(c, scene_alloc(S, Scene::kNormals, (size_t)S.nnorm * sizeof(float4), pool));
+            HIPC(c, hipMemcpyAsync(S.normals(), normals, (size_t)S.nnorm * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+            d_normals = S.normals();
         }
     }
     rtrefit::DevArgs a{};
-    a.wnodes = c->d_wnodes; a.tris = c->d_tris; a.shade = c->d_shade; a.leaf_table = c->d_leaf;
+    a.wnodes = S.wnodes(); a.tris = S.tris(); a.shade = S.shade(); a.leaf_table = S.leaf();
     a.verts = d_verts; a.normals = d_normals;
-    a.idx = r.d_idx; a.normal_idx = r.d_normal_idx; a.ref_tri = r.d_ref_tri;
-    a.level_ids = r.d_level_ids; a.level_begin = r.d_level_begin; a.out = r.d_out;
-    a.nref = r.nref; a.ntri = r.ntri; a.n_inner = c->n_inner; a.root = c->root;
+    a.idx = S.idx(); a.normal_idx = S.normal_idx(); a.ref_tri = S.ref_tri();
+    a.level_ids = S.level_ids(); a.level_begin = S.d_level_begin(); a.out = S.out();
+    a.nref = S.nref; a.ntri = S.ntri; a.n_inner = S.n_inner; a.root = S.root;
     HIPC(c, hipEventRecord(r.ev[0], c->stream));
-    HIPC(c, rtrefit::launch(a, r.level_begin.data(), (uint32_t)r.level_begin.size() - 1u, c->stream, &r.launches));
+    HIPC(c, rtrefit::launch(a, S.level_begin.data(), (uint32_t)S.level_begin.size() - 1u, c->stream, &r.launches));
     HIPC(c, hipEventRecord(r.ev[1], c->stream));
     uint32_t out[8] = {};
-    HIPC(c, hipMemcpyAsync(out, r.d_out, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipMemcpyAsync(out, S.out(), sizeof out, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, wait_stream(c->stream));
     r.timed = true;
-    c->fast_div = out[0] ? 1 : 0;
+    S.fast_div = out[0] ? 1 : 0;
     float box[6];
     std::memcpy(box, out + 2, sizeof box);
-    c->bounds_min.x = box[0]; c->bounds_min.y = box[1]; c->bounds_min.z = box[2];
-    c->bounds_max.x = box[3]; c->bounds_max.y = box[4]; c->bounds_max.z = box[5];
+    S.bounds_min.x = box[0]; S.bounds_min.y = box[1]; S.bounds_min.z = box[2];
+    S.bounds_max.x = box[3]; S.bounds_max.y = box[4]; S.bounds_max.z = box[5];
     return RT_OK;
 }
 
@@ -1877,10 +1767,10 @@ int rt_update_vertices_device(rt_ctx* c, const rt_float4* d_verts, int32_t nv, c
 int rt_scene_bounds(rt_ctx* c, rt_float4* mn, rt_float4* mx) {
     if (!c || !mn || !mx) return set_err(c, "rt_scene_bounds: invalid argument", RT_ERR_INVALID_ARG);
     if (!c->have_scene) return set_err(c, "rt_scene_bounds: no scene uploaded", RT_ERR_NO_SCENE);
-    if (!c->have_bounds)
+    if (!c->scene.have_bounds)
         return set_err(c, "rt_scene_bounds: the scene came from a scene image, which carries no root box", RT_ERR_BAD_SCENE);
-    *mn = c->bounds_min;
-    *mx = c->bounds_max;
+    *mn = c->scene.bounds_min;
+    *mx = c->scene.bounds_max;
     return RT_OK;
 }
 
@@ -1986,61 +1876,9 @@ int rt_last_build_timing(rt_ctx* c, float* total_ms) {
 // ---- a renderable scene built on the GPU ----
 // rt_build_bvh's tree and rt_upload_scene's records without a host round trip: the index check,
 // rtlbvh::build into context-owned scratch, then rtscene's kernels write the records into arrays
-// of their own (NewScene).  The context takes them only when everything has succeeded (after waiting for the
-// frames in flight); until then the previous scene is untouched, and it stays on any failure.
-namespace {
-using SceneArrays = rt_ctx::SceneArrays;
-
-// What a call allocates: from the spare set where that fits, else fresh.  Unless the context takes
-// it, it goes (back) to the spare set.
-struct NewScene {
-    rt_ctx* c;
-    SceneArrays arr;
-    explicit NewScene(rt_ctx* ctx) : c(ctx) {}
-    NewScene(const NewScene&) = delete;
-    NewScene& operator=(const NewScene&) = delete;
-    hipError_t take(int k, size_t bytes) {
-        bytes = std::max<size_t>(bytes, 16);
-        SceneArrays& sp = c->spare;
-        if (sp.p[k] && sp.cap[k] >= bytes) {
-            arr.p[k] = sp.p[k]; arr.cap[k] = sp.cap[k];
-            sp.p[k] = nullptr; sp.cap[k] = 0;
-            return hipSuccess;
-        }
-        const hipError_t e = hipMalloc(&arr.p[k], bytes);
-        if (e != hipSuccess) arr.p[k] = nullptr; else arr.cap[k] = bytes;
-        return e;
-    }
-    ~NewScene() {
-        for (int k = 0; k < SceneArrays::kCount; ++k) {
-            if (!arr.p[k]) continue;
-            if (!c->spare.p[k]) { c->spare.p[k] = arr.p[k]; c->spare.cap[k] = arr.cap[k]; }
-            else (void)hipFree(arr.p[k]);
-        }
-    }
-};
-}  // namespace
-
-// The arrays of a scene rt_build_scene built go to the spare set (the caller has waited for the
-// frames in flight); free_scene then finds nothing of them.
-static void stash_scene(rt_ctx* c) {
-    SceneArrays& b = c->built;
-    if (!c->have_scene || !b.p[SceneArrays::kRec] || b.p[SceneArrays::kRec] != (void*)c->d_wnodes) return;
-    for (int k = 0; k < SceneArrays::kCount; ++k) {
-        if (!b.p[k]) continue;
-        if (c->spare.p[k]) (void)hipFree(c->spare.p[k]);
-        c->spare.p[k] = b.p[k];
-        c->spare.cap[k] = b.cap[k];
-    }
-    rt_ctx::Refit& r = c->refit;
-    c->d_wnodes = nullptr; c->d_tris = nullptr; c->d_shade = nullptr; c->d_leaf = nullptr;
-    r.d_idx = r.d_normal_idx = r.d_ref_tri = nullptr;
-    r.d_level_ids = r.d_level_begin = r.d_out = nullptr;
-    if (b.p[SceneArrays::kVerts]) r.d_verts = nullptr;
-    if (b.p[SceneArrays::kNormals]) r.d_normals = nullptr;
-    b = SceneArrays{};
-}
-
+// of their own, taken from the spare pool where they fit.  install_scene hands them to the context
+// only when everything has succeeded; until then the previous scene is untouched, and it stays on
+// any failure, when the new arrays go (back) to the pool.
 static int build_scene(rt_ctx* c, const char* who, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx,
                        int32_t max_leaf_arg, const rt_float4* normals, int32_t nnorm, const int32_t* normal_idx,
                        const rt_material* mats, int32_t nmat, const int32_t* tri_to_mat, bool on_device, void* stream) {
@@ -2079,16 +1917,14 @@ static int build_scene(rt_ctx* c, const char* who, const rt_float4* verts, int32
     };
     auto oom = [&] { return fail(RT_ERR_OUT_OF_MEMORY, std::string(who) + ": out of device memory"); };
 
-    using A = SceneArrays;
-    NewScene ns(c);
-    if (ns.take(A::kIdx, (size_t)nidx * 4) != hipSuccess || ns.take(A::kNormalIdx, (size_t)nidx * 4) != hipSuccess ||
-        ns.take(A::kRefTri, (size_t)n * 4) != hipSuccess || ns.take(A::kOut, 32) != hipSuccess ||
+    PendingScene ps(&c->spare);
+    Scene& N = ps.s;
+    auto take = [&](int k, size_t bytes) { return scene_alloc(N, k, bytes, ps.pool); };
+    if (take(Scene::kIdx, (size_t)nidx * 4) != hipSuccess || take(Scene::kNormalIdx, (size_t)nidx * 4) != hipSuccess ||
+        take(Scene::kRefTri, (size_t)n * 4) != hipSuccess || take(Scene::kOut, 32) != hipSuccess ||
         rtlbvh::reserve(W.mats, (size_t)nmat * sizeof(rt_material)) != hipSuccess ||
         rtlbvh::reserve(S.nodes, (size_t)(2 * (int64_t)n - 1) * sizeof(rt_bvh_node)) != hipSuccess)
         return oom();
-    int32_t *new_idx = (int32_t*)ns.arr.p[A::kIdx], *new_normal_idx = (int32_t*)ns.arr.p[A::kNormalIdx];
-    int32_t* new_ref_tri = (int32_t*)ns.arr.p[A::kRefTri];
-    uint32_t* new_out = (uint32_t*)ns.arr.p[A::kOut];
     const float4* d_verts = (const float4*)verts;
     const float4* d_normals = (const float4*)normals;
     const int32_t* d_tri_to_mat = tri_to_mat;
@@ -2098,58 +1934,51 @@ static int build_scene(rt_ctx* c, const char* who, const rt_float4* verts, int32
         HIPC(c, hipStreamWaitEvent(c->stream, W.ev[2], 0));
     } else {
         kind = hipMemcpyHostToDevice;
-        if (ns.take(A::kVerts, (size_t)nv * sizeof(float4)) != hipSuccess ||
-            ns.take(A::kNormals, (size_t)nnorm * sizeof(float4)) != hipSuccess ||
+        if (take(Scene::kVerts, (size_t)nv * sizeof(float4)) != hipSuccess ||
+            take(Scene::kNormals, (size_t)nnorm * sizeof(float4)) != hipSuccess ||
             rtlbvh::reserve(W.tri_to_mat, (size_t)n * 4) != hipSuccess)
             return oom();
-        HIPC(c, hipMemcpyAsync(ns.arr.p[A::kVerts], verts, (size_t)nv * sizeof(float4), kind, c->stream));
-        HIPC(c, hipMemcpyAsync(ns.arr.p[A::kNormals], normals, (size_t)nnorm * sizeof(float4), kind, c->stream));
+        HIPC(c, hipMemcpyAsync(N.verts(), verts, (size_t)nv * sizeof(float4), kind, c->stream));
+        HIPC(c, hipMemcpyAsync(N.normals(), normals, (size_t)nnorm * sizeof(float4), kind, c->stream));
         HIPC(c, hipMemcpyAsync(W.tri_to_mat.p, tri_to_mat, (size_t)n * 4, kind, c->stream));
-        d_verts = (const float4*)ns.arr.p[A::kVerts];
-        d_normals = (const float4*)ns.arr.p[A::kNormals];
+        d_verts = N.verts();
+        d_normals = N.normals();
         d_tri_to_mat = (const int32_t*)W.tri_to_mat.p;
     }
     // the scene's own copies of the index arrays (rt_update_vertices reads them)
-    HIPC(c, hipMemcpyAsync(new_idx, idx, (size_t)nidx * 4, kind, c->stream));
-    HIPC(c, hipMemcpyAsync(new_normal_idx, normal_idx, (size_t)nidx * 4, kind, c->stream));
+    HIPC(c, hipMemcpyAsync(N.idx(), idx, (size_t)nidx * 4, kind, c->stream));
+    HIPC(c, hipMemcpyAsync(N.normal_idx(), normal_idx, (size_t)nidx * 4, kind, c->stream));
     HIPC(c, hipMemcpyAsync(W.mats.p, mats, (size_t)nmat * sizeof(rt_material), hipMemcpyHostToDevice, c->stream));
 
     HIPC(c, hipEventRecord(W.ev[0], c->stream));
     std::string err;
     uint32_t bad = 0;
-    int rc = rtscene::check(W, c->stream, new_idx, nv, new_normal_idx, nnorm, d_tri_to_mat, nmat, n, &bad, err);
+    int rc = rtscene::check(W, c->stream, N.idx(), nv, N.normal_idx(), nnorm, d_tri_to_mat, nmat, n, &bad, err);
     if (rc != RT_OK) return fail(rc, std::string(who) + ": " + err);
     if (bad)
         return fail(RT_ERR_BAD_SCENE, bad & rtscene::kBadVerts     ? "mesh_indices out of range"
                                       : bad & rtscene::kBadNormals ? "mesh_normals_indices out of range"
                                                                    : "tri_to_material out of range");
     int32_t nn = 0;
-    rc = rtlbvh::build(S, c->stream, d_verts, nv, new_idx, n, max_leaf, extent_keys, (float4*)S.nodes.p, 2 * n - 1, new_ref_tri,
-                       &nn, err);
+    rc = rtlbvh::build(S, c->stream, d_verts, nv, N.idx(), n, max_leaf, extent_keys, (float4*)S.nodes.p, 2 * n - 1,
+                       N.ref_tri(), &nn, err);
     if (rc != RT_OK) return fail(rc, rc == RT_ERR_BAD_SCENE ? err : std::string(who) + ": " + err);
     const uint32_t K = (uint32_t)(nn - 1) / 2u;
-    const size_t n_wnodes4 = (size_t)std::max<uint32_t>(K, 1u) * 4, n_tris4 = (size_t)n * 3 + 1, n_shade4 = (size_t)n * 7;
-    // inner and triangle records in one allocation, or two: alloc_records' layout and rule
-    const bool split = records_split(n_wnodes4, n_tris4);
-    if (ns.take(A::kRec, (split ? n_wnodes4 : n_wnodes4 + n_tris4) * sizeof(float4)) != hipSuccess ||
-        (split && ns.take(A::kTris, n_tris4 * sizeof(float4)) != hipSuccess) ||
-        ns.take(A::kShade, n_shade4 * sizeof(float4)) != hipSuccess || ns.take(A::kLeaf, sizeof(int2)) != hipSuccess ||
-        ns.take(A::kLevelIds, (size_t)K * 4) != hipSuccess)
+    if (scene_alloc_records(N, (size_t)std::max<uint32_t>(K, 1u) * 4, (size_t)n * 3 + 1, (size_t)n * 7, 1, ps.pool) != hipSuccess ||
+        take(Scene::kLevelIds, (size_t)K * 4) != hipSuccess)
         return oom();
-    float4* new_wnodes = (float4*)ns.arr.p[A::kRec];
-    float4* new_tris = split ? (float4*)ns.arr.p[A::kTris] : new_wnodes + n_wnodes4;
-    HIPC(c, hipMemsetAsync(new_tris + (size_t)n * 3, 0, sizeof(float4), c->stream));   // the trailing pad
-    HIPC(c, hipMemsetAsync(ns.arr.p[A::kLeaf], 0, sizeof(int2), c->stream));           // no escape leaves: {0, 0}
+    HIPC(c, hipMemsetAsync(N.tris() + (size_t)n * 3, 0, sizeof(float4), c->stream));   // the trailing pad
+    HIPC(c, hipMemsetAsync(N.leaf(), 0, sizeof(int2), c->stream));                      // no escape leaves: {0, 0}
     rtscene::Args a{};
-    a.verts = d_verts; a.normals = d_normals; a.idx = new_idx; a.normal_idx = new_normal_idx; a.tri_to_mat = d_tri_to_mat;
-    a.mats = (const float4*)W.mats.p; a.nodes = (const float4*)S.nodes.p; a.refs = new_ref_tri;
+    a.verts = d_verts; a.normals = d_normals; a.idx = N.idx(); a.normal_idx = N.normal_idx(); a.tri_to_mat = d_tri_to_mat;
+    a.mats = (const float4*)W.mats.p; a.nodes = (const float4*)S.nodes.p; a.refs = N.ref_tri();
     a.n = n; a.max_leaf = max_leaf; a.K = K;
-    a.wnodes = new_wnodes; a.tris = new_tris; a.shade = (float4*)ns.arr.p[A::kShade];
-    a.level_ids = (uint32_t*)ns.arr.p[A::kLevelIds]; a.out = new_out;
-    std::vector<uint32_t> level_begin;
+    a.wnodes = N.wnodes(); a.tris = N.tris(); a.shade = N.shade();
+    a.level_ids = N.level_ids(); a.out = N.out();
+    std::vector<uint32_t>& level_begin = N.level_begin;
     uint32_t out[8] = {1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     if (K == 0) {   // the root is a leaf: no inner record, four zero float4s in its place
-        HIPC(c, hipMemsetAsync(new_wnodes, 0, 4 * sizeof(float4), c->stream));
+        HIPC(c, hipMemsetAsync(N.wnodes(), 0, 4 * sizeof(float4), c->stream));
         rc = rtscene::leaf_records(W, c->stream, a, err);
         level_begin.assign(1, 0u);
     } else {
@@ -2159,45 +1988,29 @@ static int build_scene(rt_ctx* c, const char* who, const rt_float4* verts, int32
     HIPC(c, hipEventRecord(W.ev[1], c->stream));
     rt_bvh_node root_leaf{};
     if (K == 0) HIPC(c, hipMemcpyAsync(&root_leaf, S.nodes.p, sizeof root_leaf, hipMemcpyDeviceToHost, c->stream));
-    else HIPC(c, hipMemcpyAsync(out, new_out, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    else HIPC(c, hipMemcpyAsync(out, N.out(), sizeof out, hipMemcpyDeviceToHost, c->stream));
     if (wait_stream(c->stream) != hipSuccess) return fail(RT_ERR_DEVICE, std::string(who) + ": the build's kernels failed");
     if (K == 0) {
         const float box[6] = {root_leaf.min.x, root_leaf.min.y, root_leaf.min.z, root_leaf.max.x, root_leaf.max.y, root_leaf.max.z};
         std::memcpy(out + 2, box, sizeof box);
-        HIPC(c, hipMemcpy(new_out, out, sizeof out, hipMemcpyHostToDevice));
+        HIPC(c, hipMemcpy(N.out(), out, sizeof out, hipMemcpyHostToDevice));
     }
-    if (ns.take(A::kLevelBegin, 67 * 4) != hipSuccess) return oom();   // (every plan fits: at most 66 heights)
-    HIPC(c, hipMemcpy(ns.arr.p[A::kLevelBegin], level_begin.data(), level_begin.size() * 4, hipMemcpyHostToDevice));
+    if (take(Scene::kLevelBegin, 67 * 4) != hipSuccess) return oom();   // (every plan fits: at most 66 heights)
+    HIPC(c, hipMemcpy(N.d_level_begin(), level_begin.data(), level_begin.size() * 4, hipMemcpyHostToDevice));
 
-    // the context takes the new scene
-    for (auto& f : c->slots)
-        if (f.idle) HIPC(c, hipEventSynchronize(f.idle));   // frames in flight still read the old scene
-    stash_scene(c);
-    free_scene(c);
-    c->d_wnodes = new_wnodes; c->d_tris = new_tris; c->split_records = split;
-    c->d_shade = (float4*)ns.arr.p[A::kShade]; c->d_leaf = (int2*)ns.arr.p[A::kLeaf];
-    c->n_wnodes4 = n_wnodes4; c->n_tris4 = n_tris4; c->n_shade4 = n_shade4; c->n_leaf = 1;
-    c->root = K ? 0u : (rtk::kLeafBit | ((uint32_t)n << 26));   // the root's record is the breadth-first order's first
-    c->n_inner = K;
-    c->fast_div = out[0] ? 1 : 0;
-    c->clean = 1;
-    c->have_scene = true;
-    ++c->scene_gen;
+    N.root = K ? 0u : rtrec::leaf_ref((uint32_t)n, 0u);   // the root's record is the breadth-first order's first
+    N.n_inner = K;
+    N.fast_div = out[0] ? 1 : 0;
+    N.clean = 1;
     float box[6];
     std::memcpy(box, out + 2, sizeof box);
-    c->bounds_min = rt_float4{box[0], box[1], box[2], 1.0f};
-    c->bounds_max = rt_float4{box[3], box[4], box[5], 1.0f};
-    c->have_bounds = true;
-    rt_ctx::Refit& r = c->refit;
-    r.d_idx = new_idx; r.d_normal_idx = new_normal_idx; r.d_ref_tri = new_ref_tri;
-    r.d_level_ids = (uint32_t*)ns.arr.p[A::kLevelIds]; r.d_level_begin = (uint32_t*)ns.arr.p[A::kLevelBegin]; r.d_out = new_out;
-    r.d_verts = (float4*)ns.arr.p[A::kVerts]; r.d_normals = (float4*)ns.arr.p[A::kNormals];   // the host form's staging
-    r.level_begin = level_begin;
-    r.nv = nv; r.nnorm = nnorm; r.nref = (uint32_t)n; r.ntri = (uint32_t)n;
-    r.why.clear();
-    r.have = true;
-    c->built = ns.arr;
-    ns.arr = SceneArrays{};   // (the context took them)
+    N.bounds_min = rt_float4{box[0], box[1], box[2], 1.0f};
+    N.bounds_max = rt_float4{box[3], box[4], box[5], 1.0f};
+    N.have_bounds = true;
+    N.nv = nv; N.nnorm = nnorm; N.nref = (uint32_t)n; N.ntri = (uint32_t)n;
+    N.why.clear();
+    N.refittable = true;
+    if (const int rc2 = install_scene(c, std::move(N))) return rc2;   // the context takes the new scene
     W.timed = true;
     return RT_OK;
 }
@@ -2228,8 +2041,8 @@ int rt_refit_level_counts(rt_ctx* c, uint32_t* counts, int32_t cap, int32_t* hei
     if (!c || !heights || cap < 0 || (cap > 0 && !counts))
         return set_err(c, "rt_refit_level_counts: invalid argument", RT_ERR_INVALID_ARG);
     if (!c->have_scene) return set_err(c, "rt_refit_level_counts: no scene uploaded", RT_ERR_NO_SCENE);
-    const rt_ctx::Refit& r = c->refit;
-    if (!r.have || r.level_begin.empty())
+    const Scene& r = c->scene;
+    if (!r.refittable || r.level_begin.empty())
         return set_err(c, "rt_refit_level_counts: the scene has no refit data (" + r.why + ")", RT_ERR_BAD_SCENE);
     const int32_t h = (int32_t)r.level_begin.size() - 1;
     for (int32_t i = 0; i < h && i < cap; ++i) counts[i] = r.level_begin[i + 1] - r.level_begin[i];
@@ -2248,18 +2061,19 @@ int rt_scene_sah(rt_ctx* c, double* inner_area, double* leaf_area_tris, double* 
         const float dx = mx[0] - mn[0], dy = mx[1] - mn[1], dz = mx[2] - mn[2];
         return (double)((dx * dy + dy * dz) + dz * dx);
     };
-    const float bmn[3] = {c->bounds_min.x, c->bounds_min.y, c->bounds_min.z};
-    const float bmx[3] = {c->bounds_max.x, c->bounds_max.y, c->bounds_max.z};
+    const Scene& S = c->scene;
+    const float bmn[3] = {S.bounds_min.x, S.bounds_min.y, S.bounds_min.z};
+    const float bmx[3] = {S.bounds_max.x, S.bounds_max.y, S.bounds_max.z};
     HIPC(c, hipSetDevice(c->device));
-    if (c->n_inner == 0) {   // the root is a leaf: its box is the scene's, its count the reference's
-        if (!c->have_bounds)
+    if (S.n_inner == 0) {   // the root is a leaf: its box is the scene's, its count the reference's
+        if (!S.have_bounds)
             return set_err(c, "rt_scene_sah: a root-leaf scene from a scene image carries no box", RT_ERR_BAD_SCENE);
-        int64_t cnt = (c->root >> 26) & 31u;
-        if (!(c->root & rtk::kLeafBit)) cnt = 0;
-        if ((uint32_t)cnt == rtk::kCntEscape) {
-            const uint32_t e = c->root & 0x03FFFFFFu;
+        int64_t cnt = rtrec::ref_count(S.root);
+        if (!(S.root & rtrec::kLeafBit)) cnt = 0;
+        if ((uint32_t)cnt == rtrec::kCntEscape) {
+            const uint32_t e = rtrec::ref_offset(S.root);
             int2 entry = make_int2(0, 0);
-            if (e < c->n_leaf) HIPC(c, hipMemcpy(&entry, c->d_leaf + e, sizeof entry, hipMemcpyDeviceToHost));
+            if (e < S.n_leaf) HIPC(c, hipMemcpy(&entry, S.leaf() + e, sizeof entry, hipMemcpyDeviceToHost));
             cnt = std::max(entry.y, 0);
         }
         *root_area = half_area(bmn, bmx);
@@ -2267,7 +2081,7 @@ int rt_scene_sah(rt_ctx* c, double* inner_area, double* leaf_area_tris, double* 
         *leaf_area_tris = *root_area * (double)cnt;
         return RT_OK;
     }
-    const uint32_t n_inner = (uint32_t)std::min<size_t>(c->n_inner, c->n_wnodes4 / 4);   // (an image's header is not trusted)
+    const uint32_t n_inner = (uint32_t)std::min<size_t>(S.n_inner, S.n_wnodes4 / 4);   // (an image's header is not trusted)
     const uint32_t nblocks = rtsah::blocks_for(n_inner);
     if (rtlbvh::reserve(c->sah_part, 2 * (size_t)nblocks * sizeof(double)) != hipSuccess ||
         rtlbvh::reserve(c->sah_out, sizeof(rtsah::Result)) != hipSuccess) {
@@ -2276,12 +2090,12 @@ int rt_scene_sah(rt_ctx* c, double* inner_area, double* leaf_area_tris, double* 
     }
     rtsah::Result res{};
     HIPC(c, hipMemsetAsync(c->sah_out.p, 0, sizeof res, c->stream));
-    HIPC(c, rtsah::launch(c->d_wnodes, n_inner, c->d_leaf, (uint32_t)c->n_leaf, c->root, (double*)c->sah_part.p,
+    HIPC(c, rtsah::launch(S.wnodes(), n_inner, S.leaf(), (uint32_t)S.n_leaf, S.root, (double*)c->sah_part.p,
                           (rtsah::Result*)c->sah_out.p, c->stream));
     HIPC(c, hipMemcpyAsync(&res, c->sah_out.p, sizeof res, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, wait_stream(c->stream));
     // rt_scene_bounds' box; a scene image carries none: the root record's own box, the union of its two slots
-    *root_area = c->have_bounds ? half_area(bmn, bmx) : half_area(res.root_box, res.root_box + 3);
+    *root_area = S.have_bounds ? half_area(bmn, bmx) : half_area(res.root_box, res.root_box + 3);
     *inner_area = *root_area + res.inner_area;
     *leaf_area_tris = res.leaf_area_tris;
     return RT_OK;
@@ -2310,7 +2124,8 @@ uint64_t image_bytes(const ImageHeader& h) {
 int rt_scene_image_size(rt_ctx* c, uint64_t* bytes) {
     if (!c || !bytes) return RT_ERR_INVALID_ARG;
     if (!c->have_scene) return set_err(c, "rt_scene_image_size: no scene uploaded", RT_ERR_NO_SCENE);
-    ImageHeader h{kImageMagic, kImageVersion, c->n_wnodes4, c->n_tris4, c->n_shade4, c->n_leaf, 0, 0, 0, 0};
+    const Scene& S = c->scene;
+    ImageHeader h{kImageMagic, kImageVersion, S.n_wnodes4, S.n_tris4, S.n_shade4, S.n_leaf, 0, 0, 0, 0};
     *bytes = image_bytes(h);
     return RT_OK;
 }
@@ -2318,17 +2133,16 @@ int rt_scene_image_size(rt_ctx* c, uint64_t* bytes) {
 int rt_scene_image_pack(rt_ctx* c, void* d_image, uint64_t bytes, void* stream) {
     if (!c || !d_image) return RT_ERR_INVALID_ARG;
     if (!c->have_scene) return set_err(c, "rt_scene_image_pack: no scene uploaded", RT_ERR_NO_SCENE);
-    const ImageHeader h{kImageMagic, kImageVersion, c->n_wnodes4, c->n_tris4, c->n_shade4, c->n_leaf,
-                        c->root, c->n_inner, c->fast_div, c->clean};
+    const Scene& S = c->scene;
+    const ImageHeader h{kImageMagic, kImageVersion, S.n_wnodes4, S.n_tris4, S.n_shade4, S.n_leaf,
+                        S.root, S.n_inner, S.fast_div, S.clean};
     if (bytes < image_bytes(h)) return set_err(c, "rt_scene_image_pack: buffer too small", RT_ERR_INVALID_ARG);
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     uint8_t* p = (uint8_t*)d_image;
     HIPC(c, hipMemcpyAsync(p, &h, sizeof h, hipMemcpyHostToDevice, s));
     p += 256;
-    const std::pair<const void*, uint64_t> parts[] = {{c->d_wnodes, h.n_wnodes4 * 16}, {c->d_tris, h.n_tris4 * 16},
-                                                      {c->d_shade, h.n_shade4 * 16}, {c->d_leaf, h.n_leaf * 8}};
-    for (const auto& q : parts) {
+    for (const auto& q : S.sections()) {
         HIPC(c, hipMemcpyAsync(p, q.first, q.second, hipMemcpyDeviceToDevice, s));
         p += sect(q.second);
     }
@@ -2346,29 +2160,19 @@ int rt_scene_image_load(rt_ctx* c, const void* d_image, uint64_t bytes, void* st
     if (h.magic != kImageMagic || h.version != kImageVersion || image_bytes(h) > bytes || h.n_wnodes4 == 0 || h.n_tris4 == 0 ||
         h.n_leaf == 0)
         return set_err(c, "rt_scene_image_load: not a scene image", RT_ERR_BAD_SCENE);
-    for (auto& f : c->slots)
-        if (f.idle) HIPC(c, hipEventSynchronize(f.idle));   // frames in flight still read the old scene
-    free_scene(c);
-    HIPC(c, alloc_records(c, h.n_wnodes4, h.n_tris4));
-    HIPC(c, hipMalloc((void**)&c->d_shade, std::max<uint64_t>(h.n_shade4, 1) * 16));
-    HIPC(c, hipMalloc((void**)&c->d_leaf, h.n_leaf * 8));
+    if (const int rc = drop_scene(c)) return rc;   // before the new one is allocated: peak memory is one scene's
+    PendingScene ps(nullptr);
+    Scene& S = ps.s;
+    HIPC(c, scene_alloc_records(S, h.n_wnodes4, h.n_tris4, h.n_shade4, h.n_leaf, nullptr));
     const uint8_t* p = (const uint8_t*)d_image + 256;
-    const std::pair<void*, uint64_t> parts[] = {{c->d_wnodes, h.n_wnodes4 * 16}, {c->d_tris, h.n_tris4 * 16},
-                                                {c->d_shade, h.n_shade4 * 16}, {c->d_leaf, h.n_leaf * 8}};
-    for (const auto& q : parts) {
+    for (const auto& q : S.sections()) {
         HIPC(c, hipMemcpyAsync(q.first, p, q.second, hipMemcpyDeviceToDevice, s));
         p += sect(q.second);
     }
     HIPC(c, hipStreamSynchronize(s));
-    c->n_wnodes4 = h.n_wnodes4; c->n_tris4 = h.n_tris4; c->n_shade4 = h.n_shade4; c->n_leaf = h.n_leaf;
-    c->root = h.root;
-    c->n_inner = h.n_inner;
-    c->fast_div = h.fast_div;
-    c->clean = h.clean;
-    c->refit.why = "the scene came from rt_scene_image_load; upload it with rt_upload_scene to update it";
-    c->have_scene = true;
-    ++c->scene_gen;
-    return RT_OK;
+    S.root = h.root; S.n_inner = h.n_inner; S.fast_div = h.fast_div; S.clean = h.clean;
+    S.why = "the scene came from rt_scene_image_load; upload it with rt_upload_scene to update it";
+    return install_scene(c, std::move(S));   // (an image carries no root box: have_bounds stays false)
 }
 
 int rt_set_params(rt_ctx* c, const rt_params* p) {
@@ -2470,16 +2274,17 @@ static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint3
     F.tiles_y = (F.local_rows + rtk::kBlockPx - 1) / rtk::kBlockPx;
     F.num_blocks = F.tiles_x * F.tiles_y;
 
-    rtk::DevScene S{c->d_wnodes,
-                    c->d_tris,
-                    c->d_shade,
-                    c->d_leaf,
-                    (uint32_t)(c->n_wnodes4 * 16),
-                    (uint32_t)((c->n_wnodes4 + c->n_tris4) * 16),
-                    c->root,
-                    c->n_inner,
-                    (c->fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,
-                    c->clean};
+    const Scene& sc = c->scene;
+    rtk::DevScene S{sc.wnodes(),
+                    sc.tris(),
+                    sc.shade(),
+                    sc.leaf(),
+                    (uint32_t)(sc.n_wnodes4 * 16),
+                    (uint32_t)((sc.n_wnodes4 + sc.n_tris4) * 16),
+                    sc.root,
+                    sc.n_inner,
+                    (sc.fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,
+                    sc.clean};
     rtk::Outputs O;
     O.out = d_out;
     O.hits = aux ? d_aux->hits : nullptr;
@@ -2596,7 +2401,7 @@ static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint3
     }
     // the fast kernels (any quotient domain: traverse_fast picks the variant) need a clean scene
     // whose records one buffer descriptor covers
-    const bool fast = S.clean != 0 && !c->split_records;
+    const bool fast = S.clean != 0 && !sc.split;
     const dim3 grid(F.num_blocks * K), block(rtk::kBlockThreads);
     int ax = aux ? 1 : 0;
     // A frame of one launch (depth 1, or the fused kernel) with RTK_EXT_EVENTS takes its timing
@@ -2942,8 +2747,8 @@ int rt_last_deferred(rt_ctx* c, uint32_t* count) {
 int rt_fetch_counts(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint32_t flags, uint64_t* out8) {
     if (!c || !out8 || w == 0 || h == 0 || depth < 1 || depth > RT_MAX_DEPTH)
         return set_err(c, "rt_fetch_counts: invalid argument", RT_ERR_INVALID_ARG);
-    if ((depth > 1 && !(flags & RT_FLAG_WAVEFRONT)) || (flags & RT_FLAG_EXACT_DIV) || !c->have_scene || !c->clean ||
-        c->split_records)
+    if ((depth > 1 && !(flags & RT_FLAG_WAVEFRONT)) || (flags & RT_FLAG_EXACT_DIV) || !c->have_scene || !c->scene.clean ||
+        c->scene.split)
         return set_err(c, "rt_fetch_counts: the fast kernels of a clean scene, depth 1 or the wavefront path",
                        RT_ERR_INVALID_ARG);
     HIPC(c, hipSetDevice(c->device));
@@ -3079,36 +2884,25 @@ int rt_scene_copy(rt_ctx* dst, rt_ctx* src) {
     if (dst == src) return RT_OK;
     if (!src->have_scene) return set_err(dst, "rt_scene_copy: the source context has no scene", RT_ERR_NO_SCENE);
     HIPC(dst, hipSetDevice(dst->device));
-    for (auto& f : dst->slots)
-        if (f.idle) HIPC(dst, hipEventSynchronize(f.idle));   // frames in flight still read the old scene
-    free_scene(dst);
-    HIPC(dst, alloc_records(dst, src->n_wnodes4, src->n_tris4));
-    HIPC(dst, hipMalloc((void**)&dst->d_shade, std::max<size_t>(src->n_shade4, 1) * 16));
-    HIPC(dst, hipMalloc((void**)&dst->d_leaf, src->n_leaf * 8));
+    if (const int rc = drop_scene(dst)) return rc;   // before the new one is allocated: peak memory is one scene's
+    const Scene& F = src->scene;
+    PendingScene ps(nullptr);
+    Scene& S = ps.s;
+    HIPC(dst, scene_alloc_records(S, F.n_wnodes4, F.n_tris4, F.n_shade4, F.n_leaf, nullptr));
     // device to device on one GPU, else peer to peer (xGMI), both on dst's stream
-    const std::pair<std::pair<void*, const void*>, size_t> parts[] = {
-        {{dst->d_wnodes, src->d_wnodes}, src->n_wnodes4 * 16}, {{dst->d_tris, src->d_tris}, src->n_tris4 * 16},
-        {{dst->d_shade, src->d_shade}, src->n_shade4 * 16}, {{dst->d_leaf, src->d_leaf}, src->n_leaf * 8}};
-    for (const auto& q : parts) {
-        if (!q.second) continue;
+    const auto to = S.sections(), from = F.sections();
+    for (size_t i = 0; i < to.size(); ++i) {
+        if (!to[i].second) continue;
         if (dst->device == src->device)
-            HIPC(dst, hipMemcpyAsync(q.first.first, q.first.second, q.second, hipMemcpyDeviceToDevice, dst->stream));
+            HIPC(dst, hipMemcpyAsync(to[i].first, from[i].first, to[i].second, hipMemcpyDeviceToDevice, dst->stream));
         else
-            HIPC(dst, hipMemcpyPeerAsync(q.first.first, dst->device, q.first.second, src->device, q.second, dst->stream));
+            HIPC(dst, hipMemcpyPeerAsync(to[i].first, dst->device, from[i].first, src->device, to[i].second, dst->stream));
     }
     HIPC(dst, hipStreamSynchronize(dst->stream));
-    dst->n_wnodes4 = src->n_wnodes4; dst->n_tris4 = src->n_tris4; dst->n_shade4 = src->n_shade4; dst->n_leaf = src->n_leaf;
-    dst->root = src->root;
-    dst->n_inner = src->n_inner;
-    dst->fast_div = src->fast_div;
-    dst->clean = src->clean;
-    dst->refit.why = "the scene came from rt_scene_copy; upload it with rt_upload_scene to update it";
-    dst->have_bounds = src->have_bounds;
-    dst->bounds_min = src->bounds_min;
-    dst->bounds_max = src->bounds_max;
-    dst->have_scene = true;
-    ++dst->scene_gen;
-    return RT_OK;
+    S.root = F.root; S.n_inner = F.n_inner; S.fast_div = F.fast_div; S.clean = F.clean;
+    S.why = "the scene came from rt_scene_copy; upload it with rt_upload_scene to update it";
+    S.have_bounds = F.have_bounds; S.bounds_min = F.bounds_min; S.bounds_max = F.bounds_max;
+    return install_scene(dst, std::move(S));
 }
 
 // rt_render_tiled: the frame is cut into 8-row bands dealt round-robin over the contexts
@@ -3339,7 +3133,7 @@ int rt_wave_timeline(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint32_t 
         frames < 1 || frames > 8 || (uint64_t)frames * (uint64_t)depth > kMaxLaunches)
         return set_err(c, "rt_wave_timeline: invalid argument", RT_ERR_INVALID_ARG);
     if ((flags & (RT_FLAG_STRICT_MATH | RT_FLAG_HW_MATH | RT_FLAG_EXACT_DIV)) || (depth > 1 && !(flags & RT_FLAG_WAVEFRONT)) ||
-        !c->have_scene || !c->clean || c->split_records)
+        !c->have_scene || !c->scene.clean || c->scene.split)
         return set_err(c, "rt_wave_timeline: the default arithmetic's fast kernels of a clean scene, depth 1 or the wavefront path",
                        RT_ERR_INVALID_ARG);
     HIPC(c, hipSetDevice(c->device));

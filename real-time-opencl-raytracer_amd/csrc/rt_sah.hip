@@ -14,13 +14,14 @@
 // No floating-point atomics and nothing handed from workgroup to workgroup inside a kernel (as
 // rt_refit.hip, rt_lbvh.hip): the result does not depend on scheduling.
 #include "rt_sah.h"
+#include "rt_records.h"
 
 namespace rtsah {
 
 namespace {
 
-constexpr uint32_t kLeafBit = 0x80000000u;   // rt_render.hip's reference encoding
-constexpr uint32_t kCntEscape = 31u;
+using rtrec::kCntEscape;
+using rtrec::kLeafBit;
 constexpr uint32_t kThreads = 256;
 
 __device__ __forceinline__ float half_area(float dx, float dy, float dz) { return (dx * dy + dy * dz) + dz * dx; }
@@ -41,9 +42,9 @@ __global__ void __launch_bounds__(kThreads) sah_sum_kernel(const float4* wnodes,
                 if (ref[c] < n_inner) inner += (double)area[c];
                 continue;
             }
-            int32_t cnt = (int32_t)((ref[c] >> 26) & 31u);
+            int32_t cnt = (int32_t)((ref[c] >> rtrec::kCntShift) & 31u);   // rtrec::ref_count, as written before it
             if ((uint32_t)cnt == kCntEscape) {
-                const uint32_t e = ref[c] & 0x03FFFFFFu;
+                const uint32_t e = rtrec::ref_offset(ref[c]);
                 cnt = e < n_leaf ? leaf_table[e].y : 0;
             }
             if (cnt > 0) leaf += (double)area[c] * (double)cnt;

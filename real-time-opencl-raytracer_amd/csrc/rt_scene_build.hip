@@ -37,12 +37,12 @@
 #include <cstddef>
 
 #include "rt_abi.h"
+#include "rt_records.h"
 
 namespace rtscene {
 
 namespace {
 
-constexpr uint32_t kLeafBit = 0x80000000u;   // rt_render.hip's reference encoding
 constexpr uint32_t kThreads = 256;
 constexpr uint32_t kBfsTop = 1024;           // rt_upload_scene's breadth-first top
 constexpr uint32_t kTopMax = 1024;           // depths with at most this many kept nodes share a launch
@@ -208,7 +208,7 @@ __device__ __forceinline__ bool coord_ok(float v) {
 __device__ __forceinline__ uint32_t ref_of(const float4* nodes, uint32_t K, const uint32_t* inner_id, uint32_t child) {
     if (child < K) return inner_id[child];
     const float4 w = nodes[3 * (size_t)child + 2];   // a leaf: 1 .. 8 references below 2^25
-    return kLeafBit | ((uint32_t)__float_as_int(w.w) << 26) | (uint32_t)__float_as_int(w.z);
+    return rtrec::leaf_ref((uint32_t)__float_as_int(w.w), (uint32_t)__float_as_int(w.z));
 }
 
 __global__ void __launch_bounds__(kThreads) inner_kernel(const float4* nodes, uint32_t K, const uint32_t* inner_id,

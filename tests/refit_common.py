@@ -140,6 +140,16 @@ def moved_vertices(name):
     return v
 
 
+def scene_image(r):
+    """The renderer's scene image, packed into a zeroed device buffer, as uint32 words."""
+    import torch
+    n = r.scene_image_size()
+    buf = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    r.pack_scene(buf.data_ptr(), n)
+    return buf.cpu().numpy().view(np.uint32)
+
+
 def with_vertices(d, verts, nodes):
     """A copy of the scene dict with other vertices and nodes."""
     e = dict(d)

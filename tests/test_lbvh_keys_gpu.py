@@ -13,7 +13,7 @@ import rtamd
 from conftest import load_golden
 from lbvh_common import cornell_first, twin
 from lbvh_keys_common import EXTENT, SMALL, mesh, np_scene_sah, twin_extent
-from refit_common import np_refit
+from refit_common import np_refit, scene_image
 
 pytestmark = pytest.mark.gpu
 
@@ -85,15 +85,6 @@ def uploaded(d, tree, verts=None):
                                         scene_max=v[:, :3].max(0)))
 
 
-def _image(r):
-    import torch
-    n = r.scene_image_size()
-    buf = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
-    torch.cuda.synchronize()
-    r.pack_scene(buf.data_ptr(), n)
-    return buf.cpu().numpy().view(np.uint32)
-
-
 def _assert_same_records(ia, ib, label):
     """test_refit_gpu's rule: word for word, but for the sign of a zero."""
     assert ia.shape == ib.shape, label
@@ -122,7 +113,7 @@ def test_built_scene_equals_an_upload_of_the_twin_and_refits(pair, name):
     d, tree = arrays(name), twin_extent(name, 2)
     a.build_scene(d, 2, keys="extent")
     b.upload(uploaded(d, tree))
-    ia, ib = _image(a), _image(b)
+    ia, ib = scene_image(a), scene_image(b)
     assert ia.shape == ib.shape
     k = np.flatnonzero(ia != ib)
     assert k.size == 0, f"{name}: {k.size} words differ, first at {k[:8]}"
@@ -135,7 +126,7 @@ def test_built_scene_equals_an_upload_of_the_twin_and_refits(pair, name):
     a.update_vertices(v2)
     want, _ = np_refit({"nodes": tree[0], "tri_indices": tree[1], "indices": d["indices"]}, v2)
     b.upload(uploaded(d, (want, tree[1]), v2))
-    _assert_same_records(_image(a), _image(b), f"{name}: after update_vertices")
+    _assert_same_records(scene_image(a), scene_image(b), f"{name}: after update_vertices")
     mn, mx = a.scene_bounds()
     assert np.array_equal(mn, want[0, 0:3]) and np.array_equal(mx, want[0, 4:7])
     _close(a.scene_sah(), np_scene_sah(want), f"{name}: refitted")

@@ -12,7 +12,7 @@ import pytest
 
 import rtamd
 from conftest import ROOT, load_golden
-from refit_common import FIXTURES, SYNTHETIC, moved_vertices, np_refit, scene_arrays, with_vertices
+from refit_common import FIXTURES, SYNTHETIC, moved_vertices, np_refit, scene_arrays, scene_image, with_vertices
 
 pytestmark = pytest.mark.gpu
 
@@ -42,16 +42,6 @@ def _scene(d, verts=None, nodes=None, normals=None):
     return rtamd.Scene.from_arrays(e)
 
 
-def _image(r):
-    """The renderer's scene image, packed into a zeroed device buffer, as uint32 words."""
-    import torch
-    n = r.scene_image_size()
-    buf = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
-    torch.cuda.synchronize()
-    r.pack_scene(buf.data_ptr(), n)
-    return buf.cpu().numpy().view(np.uint32)
-
-
 def _assert_same_records(ia, ib, label):
     """Word for word, but for the sign of a zero; the header (fast_div in it) equal."""
     assert ia.shape == ib.shape, label
@@ -74,12 +64,12 @@ def test_updated_records_equal_an_upload_of_the_cpu_refit(pair, name):
     a, b = pair
     d, v2, nodes2 = _refit_scene(name)
     a.upload(_scene(d))
-    base = _image(a)
+    base = scene_image(a)
     mn0, mx0 = a.scene_bounds()
     assert np.array_equal(mn0, d["nodes"][0, 0:3]) and np.array_equal(mx0, d["nodes"][0, 4:7])   # before any update
     a.update_vertices(v2)
     b.upload(_scene(d, v2, nodes2))
-    ia, ib = _image(a), _image(b)
+    ia, ib = scene_image(a), scene_image(b)
     assert not np.array_equal(ia, base), "the update changed nothing"
     _assert_same_records(ia, ib, name)
     want, _ = np_refit(d, v2)
@@ -92,17 +82,17 @@ def test_fast_quotient_flag_follows_the_coordinates_both_ways(pair):
     a, b = pair
     d = load_golden("rand2k")
     a.upload(_scene(d))
-    assert _image(a)[HDR_FAST_DIV] == 1
+    assert scene_image(a)[HDR_FAST_DIV] == 1
     v2 = np.array(d["vertices"], np.float32, copy=True)
     v2[0, 0] = np.float32(2.0 ** 61)          # outside the fast quotient's domain [2^-66, 2^60]
     a.update_vertices(v2)
     b.upload(_scene(d, v2, rtamd.refit_nodes(_scene(d), v2)))
-    ia, ib = _image(a), _image(b)
+    ia, ib = scene_image(a), scene_image(b)
     assert ib[HDR_FAST_DIV] == 0 and ia[HDR_FAST_DIV] == 0
     _assert_same_records(ia, ib, "2^61")
     a.update_vertices(d["vertices"])         # and back
     b.upload(_scene(d))
-    ia, ib = _image(a), _image(b)
+    ia, ib = scene_image(a), scene_image(b)
     assert ib[HDR_FAST_DIV] == 1 and ia[HDR_FAST_DIV] == 1
     _assert_same_records(ia, ib, "back to the base vertices")
 
@@ -153,7 +143,7 @@ def test_updated_scene_renders_as_the_oracle_renders_the_cpu_refit(pair, name):
     n2[:, :3] += rng.uniform(-0.3, 0.3, (n2.shape[0], 3)).astype(np.float32)
     a.update_vertices(d["vertices"], n2)
     b.upload(_scene(d, d["vertices"], rtamd.refit_nodes(_scene(d), d["vertices"]), n2))
-    _assert_same_records(_image(a), _image(b), f"{name}: base vertices, new normals")
+    _assert_same_records(scene_image(a), scene_image(b), f"{name}: base vertices, new normals")
     p0 = _boxed(d["params"], *a.scene_bounds())
     a.set_params(p0)
     b.set_params(p0)
@@ -223,7 +213,7 @@ def test_device_form_takes_vertices_written_on_a_side_stream(pair):
     a, _ = pair
     d, v2, _ = _refit_scene("hf40k")
     a.upload(_scene(d))
-    base = _image(a)
+    base = scene_image(a)
     side = torch.cuda.Stream(device="cuda:0")
     src = torch.from_numpy(d["vertices"]).to("cuda:0")
     delta = torch.from_numpy(v2 - d["vertices"]).to("cuda:0")
@@ -231,13 +221,13 @@ def test_device_form_takes_vertices_written_on_a_side_stream(pair):
     with torch.cuda.stream(side):
         dv = src + delta                              # the caller's animation kernel, on its own stream
     a.update_vertices((dv.data_ptr(), side.cuda_stream))
-    device_form = _image(a)
+    device_form = scene_image(a)
     side.synchronize()
     moved = dv.cpu().numpy()                          # what that kernel wrote
     assert not np.array_equal(moved, d["vertices"]) and not np.array_equal(device_form, base)
     a.upload(_scene(d))
     a.update_vertices(moved)
-    assert np.array_equal(_image(a), device_form)
+    assert np.array_equal(scene_image(a), device_form)
 
 
 def _read_ppm(path):

@@ -14,7 +14,7 @@ import pytest
 import rtamd
 from conftest import ROOT, load_golden
 from lbvh_common import mesh, twin
-from refit_common import np_refit
+from refit_common import np_refit, scene_image
 
 pytestmark = pytest.mark.gpu
 
@@ -85,16 +85,6 @@ def uploaded(d, tree, verts=None):
     return rtamd.Scene.from_arrays(e)
 
 
-def _image(r):
-    """The renderer's scene image, packed into a zeroed device buffer, as uint32 words."""
-    import torch
-    n = r.scene_image_size()
-    buf = torch.zeros(n, dtype=torch.uint8, device="cuda:0")
-    torch.cuda.synchronize()
-    r.pack_scene(buf.data_ptr(), n)
-    return buf.cpu().numpy().view(np.uint32)
-
-
 def _assert_equal_images(ia, ib, label):
     assert ia.shape == ib.shape, f"{label}: image sizes {ia.shape} vs {ib.shape}"
     assert np.array_equal(ia[:HDR_WORDS], ib[:HDR_WORDS]), f"{label}: headers differ: {ia[:16]} vs {ib[:16]}"
@@ -116,7 +106,7 @@ def _both(pair, d, tree, max_leaf, label):
     a, b = pair
     a.build_scene(d, max_leaf)
     b.upload(uploaded(d, tree))
-    ia, ib = _image(a), _image(b)
+    ia, ib = scene_image(a), scene_image(b)
     _assert_equal_images(ia, ib, label)
     (amn, amx), (bmn, bmx) = a.scene_bounds(), b.scene_bounds()
     assert np.array_equal(amn.view(np.uint32), bmn.view(np.uint32)), f"{label}: bounds min {amn} vs {bmn}"
@@ -174,16 +164,16 @@ def test_refit_plan_counts_and_an_update_afterwards(pair, name):
     assert np.array_equal(ca, cb), f"{name}: records per height {ca} vs {cb}"
     assert ca.sum() == (tree[0].shape[0] - 1) // 2 and (np.diff(ca.astype(np.int64)) <= 0).all()
     v2 = _moved(d, name)
-    base = _image(a)
+    base = scene_image(a)
     a.update_vertices(v2)
     b.update_vertices(v2)
-    ia, ib = _image(a), _image(b)
+    ia, ib = scene_image(a), scene_image(b)
     assert not np.array_equal(ia, base), "the update changed nothing"
     _assert_same_records(ia, ib, f"{name}: after update_vertices")
     # and both are the upload of the CPU refit
     want, _ = np_refit({"nodes": tree[0], "tri_indices": tree[1], "indices": d["indices"]}, v2)
     b.upload(uploaded(d, (want, tree[1]), v2))
-    _assert_same_records(ia, _image(b), f"{name}: against an upload of the CPU refit")
+    _assert_same_records(ia, scene_image(b), f"{name}: against an upload of the CPU refit")
     mn, mx = a.scene_bounds()
     assert np.array_equal(mn, want[0, 0:3]) and np.array_equal(mx, want[0, 4:7])
 
@@ -221,9 +211,9 @@ def test_fast_quotient_flag_follows_the_coordinates_both_ways(pair):
     v2[0, 0] = np.float32(2.0 ** 61)          # outside the fast quotient's domain [2^-66, 2^60]
     e = dict(d, vertices=v2)
     ia = _both(pair, e, twin((v2, d["indices"]), 2), 2, "2^61")
-    assert ia[HDR_FAST_DIV] == 0 and _image(b)[HDR_FAST_DIV] == 0
+    assert ia[HDR_FAST_DIV] == 0 and scene_image(b)[HDR_FAST_DIV] == 0
     ia = _both(pair, d, twin("rand2k", 2), 2, "back to the base vertices")
-    assert ia[HDR_FAST_DIV] == 1 and _image(b)[HDR_FAST_DIV] == 1
+    assert ia[HDR_FAST_DIV] == 1 and scene_image(b)[HDR_FAST_DIV] == 1
 
 
 def _device_scene(d, side, spare=0):
@@ -261,19 +251,19 @@ def test_device_form_takes_vertices_written_on_a_side_stream(pair):
         dv = keep["vertices"] + dlt                    # the caller's animation kernel, on its own stream
     dev["vertices"] = (dv.data_ptr(), side.cuda_stream)
     a.build_scene(dev, 4, **_counts(d))
-    device_form = _image(a)
+    device_form = scene_image(a)
     side.synchronize()
     moved = dv.cpu().numpy()                           # what that kernel wrote
     assert not np.array_equal(moved, d["vertices"])
     a.build_scene(dict(d, vertices=moved), 4)
-    host_form = _image(a)
+    host_form = scene_image(a)
     _assert_equal_images(device_form, host_form, "device form against host form")
     a.build_scene(d, 4)
-    assert not np.array_equal(_image(a), device_form)   # the moved vertices mattered
+    assert not np.array_equal(scene_image(a), device_form)   # the moved vertices mattered
     a.update_vertices(moved)                            # and the device form left a refittable scene
     mixed = dict(dev, indices=d["indices"])             # numpy indices join the device arrays
     a.build_scene(mixed, 4, **_counts(d))
-    _assert_equal_images(_image(a), host_form, "device vertices, host indices")
+    _assert_equal_images(scene_image(a), host_form, "device vertices, host indices")
 
 
 def _raw(r, d, max_leaf, nidx=None, nnorm=None):
@@ -294,11 +284,11 @@ def test_refusals_leave_the_previous_scene(pair):
     a.set_params(g["params"])
     before = a.render(w, h, depth=3)
     assert np.count_nonzero(before) > 0
-    image = _image(a)
+    image = scene_image(a)
 
     def unchanged(label):
         assert np.array_equal(a.render(w, h, depth=3), before), label
-        assert np.array_equal(_image(a), image), label
+        assert np.array_equal(scene_image(a), image), label
 
     for kw in ({"max_leaf": 0}, {"max_leaf": 9}, {"max_leaf": 4, "nidx": 4}, {"max_leaf": 4, "nnorm": 0}):
         assert _raw(a, d, **kw) == RT_ERR_INVALID_ARG, kw
