@@ -273,41 +273,60 @@ __device__ int traverse(const DevScene& S, const Ray& ray, float& tHit, const St
 // Stack entries 0..sc-3 live in this lane's LDS column, so slot sc-2 is always free:
 // every inner visit writes `nxt` there unconditionally (a push keeps it) and reads slot
 // sc-3 (what a pop needs) before it knows whether it pops; push / advance / pop are
-// selects.  A stack deeper than the LDS part returns false: the caller restarts the ray
-// with the general traversal (same result).
+// selects.  The stack count travels as `sb` = kStackBase + (sc - 1) * 256: slot sc - 3 is
+// that many bytes (less kStackBase) above the column's lowest guard row (rtk::kLdsGuard), the
+// read is at that address, the write 256 B above it, a push or pop moves sb by 256, and no
+// address is clamped.  A lane is in the loop while (int)sb >= kStackBase.  kStackBase is
+// chosen so that the push to sc = kLdsStack + 2, the first stack deeper than the LDS part,
+// carries sb into the sign bit: the lane leaves the loop by the loop's own compare, before
+// any row past its column is touched, and sb < 0 afterwards says that the caller must restart
+// the ray with the general traversal (same result).  A pop from sc = 1 and kStackDone (an
+// any-hit's first hit) leave it with 0 <= sb < kStackBase.
 // MODE 0: packed fast quotient; 1: + Markstein's zero-direction select (S_strict / S_hw
 // only); 2: the division form (a ray outside the fast quotient's domain).
 // ---------------------------------------------------------------------------
+constexpr uint32_t kStackBase = 0x80000000u - (uint32_t)(kLdsStack + 1) * 256u, kStackDone = 0u;
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+__device__ __forceinline__ uint32_t lds_get(int a) { return *(lds_u32*)(uintptr_t)(uint32_t)a; }
+__device__ __forceinline__ void lds_put(int a, uint32_t v) { *(lds_u32*)(uintptr_t)(uint32_t)a = v; }
+// The LDS addresses of slot sc - 3 (read) and slot sc - 2 (written) of the column whose entry 0 is at
+// col0.  GUARD: the column has its guard rows.  A kernel whose LDS has no room for them (the fused
+// kernel: 7 blocks per CU with its parked rays) clamps both to entry 0, as every kernel once did.
+template <bool GUARD> __device__ __forceinline__ int slot_get(int col0, uint32_t sb) {
+    return GUARD ? (int)((uint32_t)col0 - (kStackBase + rtk::kLdsGuard * 256u) + sb)
+                 : col0 + max((int)(sb - kStackBase) - 512, 0);
+}
+template <bool GUARD> __device__ __forceinline__ int slot_put(int get_at, int col0, uint32_t sb) {
+    return GUARD ? get_at + 256 : col0 + max((int)(sb - kStackBase) - 256, 0);
+}
+
+// put_at: the LDS address of slot sc - 2
 template <int MODE>
 __device__ __forceinline__ void inner_step(const float4& q0, const float4& q1, const float4& q2, float2 refs,
-                                           const RayPk& rp, float th, uint32_t popped, uint32_t* lds,
-                                           uint32_t& cur, uint32_t& nxt, int& sc) {
+                                           const RayPk& rp, float th, uint32_t popped, int put_at,
+                                           uint32_t& cur, uint32_t& nxt, uint32_t& sb) {
     float n0, f0, n1, f1;
     if (MODE == 2) {
         slab2_div(q0, q1, q2, F3{rp.oxy.x, rp.oxy.y, rp.ozdz.x}, F3{rp.dxy.x, rp.dxy.y, rp.ozdz.y}, n0, f0, n1, f1);
     } else {
         slab2_pk<MODE == 1>(q0, q1, q2, rp, n0, f0, n1, f1);
     }
-#if RTK_IMIN
     // (n <= f) && (n <= th) == n <= min(f, th) for every input: th is a finite hit distance, and n
     // and f are NaN together or not at all (per axis the NaN-ignoring min and max of the two slab
     // values are NaN only when both are; n and f compose those with NaN-ignoring max and min), and
-    // a NaN n fails both forms.
+    // a NaN n fails both forms.  (Three compares and two mask ANDs instead: C3 0.2978 vs 0.2914 ms,
+    // DESIGN.md 7.5.)
     const bool i0 = (n0 <= min_(f0, th)) && (f0 >= kTmin);
     const bool i1 = (n1 <= min_(f1, th)) && (f1 >= kTmin);
-#else
-    const bool i0 = (n0 <= f0) && (f0 >= kTmin) && (n0 <= th);
-    const bool i1 = (n1 <= f1) && (f1 >= kTmin) && (n1 <= th);
-#endif
     const uint32_t r0 = __float_as_uint(refs.x), r1 = __float_as_uint(refs.y);
-    lds[min(max(sc - 2, 0), kLdsStack - 1) * 64] = nxt;
+    lds_put(put_at, nxt);
     const bool both = i0 && i1, none = !i0 && !i1;
     const bool swap = n0 > n1;  // near child first, tie -> left (:901-906)
     const uint32_t nearr = swap ? r1 : r0, farr = swap ? r0 : r1, one = i0 ? r0 : r1;
     const uint32_t ncur = both ? nearr : (none ? nxt : one);
     nxt = both ? farr : (none ? popped : nxt);
     cur = ncur;
-    sc += (int)both - (int)none;
+    sb += (both ? 256u : 0u) - (none ? 256u : 0u);
 }
 
 // The ray travels in RayPk's registers only: its origin and direction are rebuilt from
@@ -332,24 +351,25 @@ __device__ __forceinline__ float2 rec_load2(__amdgpu_buffer_rsrc_t r, uint32_t o
     return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
 }
 
-template <bool CLOSEST, int MODE, int TR, bool SEL = false>
+template <bool CLOSEST, int MODE, int TR, bool SEL = false, bool GUARD = true>
 __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, float& tHit, const Stack& st,
                                               int& result) {
-    uint32_t* lds = st.lds;
+    const int col0 = (int)(uint32_t)(uintptr_t)(lds_u32*)st.lds;   // the column's entry 0, as an LDS byte address
     const RayPk rp = ray_pk(ray_io.ori, ray_io.dir, slab_recip(ray_io));
     // the packed reciprocal goes back as inv_dir: RN(1/d) itself in S_strict / S_hw, the
     // 2.5-ulp one in S_ref (after a traversal callers use only ori and dir, and the
     // general traversal recomputes slab_recip)
     const F3 inv_keep = F3{rp.yxy.x, rp.yxy.y, rp.yz.x};
     uint32_t cur = S.root, nxt = 0;
-    int sc = 1;
+    uint32_t sb = kStackBase;   // sc = 1
     int res = -1;
     float th = tHit;
-    bool deep = false;
     // leaf state as byte offsets into the record allocation: the next triangle record and
-    // the end of the leaf's range (no per-iteration multiply; < 2^31 by record_limit)
+    // the end of the leaf's range (no per-iteration multiply; < 2^31 by record_limit).
+    // tk >= tend whenever the lane is not inside a leaf: a leaf `cur` with tk >= tend is one
+    // the lane has just arrived at, and the main loop decodes it at the top of its next trip,
+    // the one place that does (the root, a child, or what a pop brought back).
     uint32_t tk = 0, tend = 0;
-    if (cur & kLeafBit) leaf_bytes(S, cur, tk, tend);
     // inner and triangle records share one allocation: buffer loads at a 32-bit byte offset
     // from one descriptor (no 64-bit address arithmetic per iteration)
     const __amdgpu_buffer_rsrc_t recs =
@@ -365,10 +385,11 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
     typedef const __attribute__((address_space(4))) su4 csu4;
     typedef const __attribute__((address_space(4))) su2 csu2;
     if (TR == 2 && CLOSEST) rtk::timeline_mark(st.fc, 6);   // the closest-hit traversal starts
-    while (sc > 0) {
+    while ((int)sb >= (int)kStackBase) {
         const uint32_t c0 = __builtin_amdgcn_readfirstlane(cur);
         if (__builtin_amdgcn_ballot_w64(cur != c0) != 0 || (c0 & kLeafBit)) break;
-        const uint32_t popped = lds[max(sc - 3, 0) * 64];
+        const int at = slot_get<GUARD>(col0, sb);
+        const uint32_t popped = lds_get(at);
         if (TR == 1) rtk::fetch_count(st.fc, false, cur, false);
         if (TR == 2) rtk::timeline_step(st.fc, CLOSEST ? 1 : 3);
         csu4* rec = (csu4*)((const char*)S.wnodes + ((size_t)c0 << 6));
@@ -378,17 +399,14 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
         const float4 q1 = make_float4(__uint_as_float(u1.x), __uint_as_float(u1.y), __uint_as_float(u1.z), __uint_as_float(u1.w));
         const float4 q2 = make_float4(__uint_as_float(u2.x), __uint_as_float(u2.y), __uint_as_float(u2.z), __uint_as_float(u2.w));
         const float2 q3 = make_float2(__uint_as_float(u3.x), __uint_as_float(u3.y));
-        inner_step<MODE>(q0, q1, q2, q3, rp, th, popped, lds, cur, nxt, sc);
-        if (sc - 2 >= kLdsStack) {
-            deep = true;
-            sc = 0;
-        }
-        if (sc > 0 && (cur & kLeafBit)) leaf_bytes(S, cur, tk, tend);
+        inner_step<MODE>(q0, q1, q2, q3, rp, th, popped, slot_put<GUARD>(at, col0, sb), cur, nxt, sb);
     }
     if (TR == 2 && CLOSEST) rtk::timeline_mark(st.fc, 7);   // its wave-uniform prologue is over
-    while (sc > 0) {
+    while ((int)sb >= (int)kStackBase) {
         const bool leaf = (cur & kLeafBit) != 0;
-        const uint32_t popped = lds[max(sc - 3, 0) * 64];
+        if (leaf && tk >= tend) leaf_bytes(S, cur, tk, tend);
+        const int at = slot_get<GUARD>(col0, sb);
+        const uint32_t popped = lds_get(at);
         // TR 1 (measurement instantiation only, rt_fetch_counts): this iteration's fetches counted;
         // TR 2 (rt_wave_timeline): the wave's loop trips counted
         if (TR == 1) rtk::fetch_count(st.fc, leaf, leaf ? (0x80000000u | tk) : cur);
@@ -417,67 +435,54 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
             asm volatile("" ::"v"(q0.x), "v"(q1.x), "v"(q2.x), "v"(q3.x));
             rtk::timeline_wait(st.fc, CLOSEST ? 0 : 1, (uint32_t)__builtin_amdgcn_s_memrealtime() - t_issue);
         }
-        bool enter = false;   // cur changed: decode it if it is a leaf
         if (!leaf) {
-            inner_step<MODE>(q0, q1, q2, q3, rp, th, popped, lds, cur, nxt, sc);
-            if (sc - 2 >= kLdsStack) {
-                deep = true;
-                sc = 0;
-            }
-            enter = true;
+            inner_step<MODE>(q0, q1, q2, q3, rp, th, popped, slot_put<GUARD>(at, col0, sb), cur, nxt, sb);
         } else {
-            // Moller-Trumbore on one reference of the leaf, in order (:965-997)
-            bool stop = false;
-            if (tk < tend) {
-                const F3 e2 = F3{q2.x, q2.y, q2.z};
-                const float t = ray_tri(ray_of(rp, inv_keep), F3{q0.x, q0.y, q0.z}, F3{q1.x, q1.y, q1.z}, e2);
-                if (t < th && t > kTmin) {
-                    th = t;
-                    res = __float_as_int(q0.w);
-                    stop = !CLOSEST;   // any-hit: first hit returns (:986)
-                }
-            }
+            // Moller-Trumbore on one reference of the leaf, in order (:965-997).  An empty leaf
+            // (tk == tend) tests the record after its range (in the allocation, or zeros) and
+            // drops the result.  Hit, advance and pop are selects: one block of bookkeeping.
+            const F3 e2 = F3{q2.x, q2.y, q2.z};
+            const float t = ray_tri(ray_of(rp, inv_keep), F3{q0.x, q0.y, q0.z}, F3{q1.x, q1.y, q1.z}, e2);
+            const bool hit = t < th && t > kTmin && tk < tend;
+            th = hit ? t : th;
+            res = hit ? __float_as_int(q0.w) : res;
             tk += 48u;
-            if (stop) {
-                sc = 0;
-            } else if (tk >= tend) {   // leaf done: pop
-                cur = nxt;
-                nxt = popped;
-                sc -= 1;
-                enter = true;
-            }
+            const bool pop = tk >= tend;   // leaf done
+            cur = pop ? nxt : cur;
+            nxt = pop ? popped : nxt;
+            sb -= pop ? 256u : 0u;
+            if (!CLOSEST) sb = hit ? kStackDone : sb;   // any-hit: first hit returns (:986)
         }
-        if (enter && sc > 0 && (cur & kLeafBit)) leaf_bytes(S, cur, tk, tend);
     }
     tHit = th;
     result = res;
     ray_io = ray_of(rp, inv_keep);
-    return !deep;
+    return (int)sb >= 0;
 }
 
 // Markstein's zero-direction select costs 12 VALU per visit and is needed by ~1e-5 of
 // rays, the division form by fewer still: a wave runs those variants only when one of
 // its rays needs them (wave-uniform branch, one code copy each).
-template <bool CLOSEST, int TR, bool SEL = false>
+template <bool CLOSEST, int TR, bool SEL = false, bool GUARD = true>
 __device__ __forceinline__ bool traverse_fast(const DevScene& S, Ray& ray, float& tHit, const Stack& st,
                                               int& result) {
     if (!S.fast_div || __builtin_amdgcn_ballot_w64(!fast_div_ok(ray)))
-        return traverse_ifif<CLOSEST, 2, TR, SEL>(S, ray, tHit, st, result);
+        return traverse_ifif<CLOSEST, 2, TR, SEL, GUARD>(S, ray, tHit, st, result);
     if (kMath != 2) {
         const bool z = ray.dir.x == 0.0f || ray.dir.y == 0.0f || ray.dir.z == 0.0f;
-        if (__builtin_amdgcn_ballot_w64(z)) return traverse_ifif<CLOSEST, 1, TR, SEL>(S, ray, tHit, st, result);
+        if (__builtin_amdgcn_ballot_w64(z)) return traverse_ifif<CLOSEST, 1, TR, SEL, GUARD>(S, ray, tHit, st, result);
     }
-    return traverse_ifif<CLOSEST, 0, TR, SEL>(S, ray, tHit, st, result);
+    return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD>(S, ray, tHit, st, result);
 }
 
 // Closest-hit / any-hit of one ray: the fast traversal, restarted with the general
 // code when its stack outgrows the LDS part (counted in O.restarts).
-template <bool CLOSEST, bool FASTONLY, int TR = 0, bool SEL = false>
+template <bool CLOSEST, bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true>
 __device__ __forceinline__ int trace(const DevScene& S, const Outputs& O, Ray& ray, float& t, const Stack& st,
                                      bool& overflow) {
     int hit;
     if (FASTONLY) {
-        if (traverse_fast<CLOSEST, TR, SEL>(S, ray, t, st, hit)) return hit;
+        if (traverse_fast<CLOSEST, TR, SEL, GUARD>(S, ray, t, st, hit)) return hit;
         atomicAdd(O.restarts, 1u);
         t = 4294967296.0f;
     }
@@ -506,14 +511,8 @@ __device__ __forceinline__ bool scene_box_hit(const Frame& F, const Ray& r) {
 __device__ __forceinline__ void shade_hit(const DevScene& S, const Frame& F, const Ray& ray, float tHit, int hit,
                                           F3& rez, F3& hitpoint, F3& normal, F3& L) {
     const F3 light_pos = F3{F.light_pos.x, F.light_pos.y, F.light_pos.z};
-#if RTK_SHADE_EXP == 2   // A/B bound only (wrong pixels): no shading-record fetch at all
-    const float4 p0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p1 = make_float4(1.0f, 0.0f, 0.0f, 0.0f),
-                 p2 = make_float4(0.0f, 0.0f, 1.0f, 0.0f), m0 = make_float4(0.0f, 1.0f, 0.0f, 0.0f), m1 = m0, m2 = m0,
-                 alb = make_float4(0.5f, 0.5f, 0.5f, 0.0f);
-#else
     const float4* sp = S.shade + (size_t)(hit / 3) * 7;
     const float4 p0 = sp[0], p1 = sp[1], p2 = sp[2], m0 = sp[3], m1 = sp[4], m2 = sp[5], alb = sp[6];
-#endif
     const F3 vNew = mad3(ray.dir, tHit - 0.001f, ray.ori);   // r.ori + r.dir * (t - 0.001f)
     normal = normalize(normal_at(vNew, xyz(p0), xyz(p1), xyz(p2), xyz(m0), xyz(m1), xyz(m2)));
     const F3 l1 = normalize(light_pos - vNew);
@@ -547,12 +546,12 @@ __device__ __forceinline__ void park_next(const F3& dir, const F3& normal, const
 }
 
 // Shadow ray from a hit (volumeRender.cl:1437-1460): any-hit, shadowed iff hit && t > 0.025.
-template <bool FASTONLY, int TR = 0, bool SEL = false>
+template <bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true>
 __device__ __forceinline__ float shadow_coef(const DevScene& S, const Outputs& O, const F3& hitpoint, const F3& L,
                                              const Stack& st, bool& overflow, int& sh) {
     Ray sray = ray_init(mad3(L, 0.001f, hitpoint), L);   // hitpoint + L * 0.001f
     float ts = 4294967296.0f;
-    sh = trace<false, FASTONLY, TR, SEL>(S, O, sray, ts, st, overflow);
+    sh = trace<false, FASTONLY, TR, SEL, GUARD>(S, O, sray, ts, st, overflow);
     return (sh >= 0 && ts > 0.025f) ? 0.25f : 1.0f;
 }
 
@@ -580,7 +579,7 @@ __device__ __forceinline__ void render_pixel(const DevScene& S, const Frame& F, 
     int ray_depth = 0;
     const bool do_shadow = !(F.flags & RT_FLAG_NO_SHADOW);
     while (cont && ray_depth < depth) {
-        const int hit = trace<true, FASTONLY>(S, O, ray, tHit, st, overflow);
+        const int hit = trace<true, FASTONLY, 0, false, false>(S, O, ray, tHit, st, overflow);
         if (want_aux) {
             O.hits[((size_t)pix * depth + ray_depth) * 2] = hit;
             O.t[(size_t)pix * depth + ray_depth] = tHit;
@@ -600,7 +599,7 @@ __device__ __forceinline__ void render_pixel(const DevScene& S, const Frame& F, 
             float coef = 1.0f;
             if (do_shadow) {
                 int sh;
-                coef = shadow_coef<FASTONLY>(S, O, hitpoint, L, st, overflow, sh);
+                coef = shadow_coef<FASTONLY, 0, false, false>(S, O, hitpoint, L, st, overflow, sh);
                 if (want_aux) O.hits[((size_t)pix * depth + kk) * 2 + 1] = sh;
             }
             shadow_sum += coef;
@@ -624,6 +623,8 @@ __device__ __forceinline__ void render_pixel(const DevScene& S, const Frame& F, 
 
 template <bool FASTONLY>
 __global__ void __launch_bounds__(256, 7) render_kernel(DevScene S, Frame F, Outputs O, int want_aux) {
+    // no guard rows (traverse_ifif's GUARD = false): with them and s_next, 24 KiB per block, only 6
+    // blocks fit a CU, and the compiler then no longer holds the kernel to 7 waves' registers
     __shared__ uint32_t s_stack[4][kLdsStack][64];
     __shared__ float s_next[4][6][64];  // next bounce's ray {o, d}, parked during the shadow trace
     const int lane = threadIdx.x & 63;
@@ -631,7 +632,6 @@ __global__ void __launch_bounds__(256, 7) render_kernel(DevScene S, Frame F, Out
     rtk::zero_next_counters(F);
     const uint32_t tb = rtk::block_tile(F);
     const uint32_t t_start = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    rtk::note_launch_start(F, t_start);
     uint32_t x, lr;
     rtk::tile_pixel(F, tb, wave, lane, x, lr);
     const uint32_t y = lr < F.local_rows ? rtk::frame_row(F, lr) : F.h;
@@ -773,15 +773,14 @@ __device__ __forceinline__ void first_bounce_pixel(const DevScene& S, const Fram
 // product kernel's wave bound.
 template <bool FASTONLY, bool NEXT, int TR = 0>
 __global__ void __launch_bounds__(256, TR == 1 ? 4 : kMath != 2 ? RTK_WF_WAVES : NEXT ? RTK_FBN_REF_WAVES : RTK_FB_WAVES) first_bounce_kernel(DevScene S, Frame F, Outputs O, WQ W, int want_aux) {
-    __shared__ uint32_t s_stack[4][kLdsStack][64];
+    __shared__ uint32_t s_stack[4][rtk::kLdsRows][64];
     __shared__ uint32_t s_fc[TR == 1 ? 8 * 256 : TR == 2 ? 4 * rtk::kTlWords : 1];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    uint32_t* lds = &s_stack[wave][0][lane];
+    uint32_t* lds = &s_stack[wave][rtk::kLdsGuard][lane];
     rtk::zero_next_counters(F);
     const uint32_t tb = rtk::block_tile(F);
     const uint32_t t_start = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    rtk::note_launch_start(F, t_start);
     uint32_t x, lr;
     rtk::tile_pixel(F, tb, wave, lane, x, lr);
     if (TR == 1)
@@ -793,7 +792,7 @@ __global__ void __launch_bounds__(256, TR == 1 ? 4 : kMath != 2 ? RTK_WF_WAVES :
     if (!NEXT) Wn.out = nullptr;   // depth 1: nothing continues
     Wn.seg = tb * 4u + (uint32_t)wave;
     Wn.seg_fill = &s_fill[wave];
-    first_bounce_pixel<FASTONLY, TR, (!NEXT || RTK_SEL_NEXT != 0), !NEXT>(S, F, O, Wn, want_aux, x, lr, lds,
+    first_bounce_pixel<FASTONLY, TR, !NEXT, !NEXT>(S, F, O, Wn, want_aux, x, lr, lds,
                                                                   TR == 1 ? &s_fc[threadIdx.x] : TR == 2 ? &s_fc[wave * rtk::kTlWords] : nullptr);
     if (NEXT) rtk::seg_close(Wn, Wn.seg);
     if (TR == 1) rtk::fetch_count_flush(s_fc, O.fcount);
@@ -818,7 +817,7 @@ __global__ void __launch_bounds__(256, TR == 1 ? 4 : kMath != 2 ? RTK_WF_WAVES :
 // Per pixel this is first_bounce_kernel's code, so every frame equals its own single render.
 template <bool FASTONLY, bool NEXT>
 __global__ void __launch_bounds__(256, kMath != 2 ? RTK_WF_WAVES : NEXT ? RTK_FBN_REF_WAVES : RTK_FB_WAVES) first_bounce_batch_kernel(DevScene S, Frame F, Outputs O, WQ W, rtk::BatchCams C) {
-    __shared__ uint32_t s_stack[4][kLdsStack][64];
+    __shared__ uint32_t s_stack[4][rtk::kLdsRows][64];
     __shared__ uint32_t s_fill[4];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -826,7 +825,6 @@ __global__ void __launch_bounds__(256, kMath != 2 ? RTK_WF_WAVES : NEXT ? RTK_FB
     const uint32_t e = rtk::block_tile(F);
     const uint32_t f = e / F.num_blocks, tb = e - f * F.num_blocks;
     const uint32_t t_start = (uint32_t)__builtin_amdgcn_s_memrealtime();
-    rtk::note_launch_start(F, t_start);
     uint32_t x, lr;
     rtk::tile_pixel(F, tb, wave, lane, x, lr);
     Frame Ff = F;
@@ -848,8 +846,8 @@ __global__ void __launch_bounds__(256, kMath != 2 ? RTK_WF_WAVES : NEXT ? RTK_FB
     const uint32_t qe = RTK_XFRAME ? tb * (gridDim.x / F.num_blocks) + f : e;
     Wn.seg = qe * 4u + (uint32_t)wave;
     Wn.seg_fill = &s_fill[wave];
-    first_bounce_pixel<FASTONLY, 0, (!NEXT || RTK_SEL_NEXT != 0), !NEXT>(S, Ff, Of, Wn, 0, x, lr, &s_stack[wave][0][lane],
-                                                                      nullptr, f * C.frame_px);
+    first_bounce_pixel<FASTONLY, 0, !NEXT, !NEXT>(S, Ff, Of, Wn, 0, x, lr, &s_stack[wave][rtk::kLdsGuard][lane], nullptr,
+                                                       f * C.frame_px);
     if (NEXT) rtk::seg_close(Wn, Wn.seg);
     tile_epilogue(F, e, t_start, &s_stack[0][0][0]);
 }
@@ -870,7 +868,7 @@ __global__ void __launch_bounds__(256, kMath != 2 ? RTK_WF_WAVES : NEXT ? RTK_FB
 // it took (in the record's tile word).
 template <bool FASTONLY, int TR = 0>
 __global__ void __launch_bounds__(256, TR == 1 ? 4 : (kMath == 2 ? RTK_WFB_REF_WAVES : RTK_WF_WAVES)) wf_bounce_kernel(DevScene S, Frame F, Outputs O, WQ W, int want_aux) {
-    __shared__ uint32_t s_stack[4][kLdsStack][64];
+    __shared__ uint32_t s_stack[4][rtk::kLdsRows][64];
     __shared__ uint32_t s_fc[TR == 1 ? 8 * 256 : TR == 2 ? 4 * rtk::kTlWords : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t t_start = TR == 2 ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
@@ -903,7 +901,7 @@ __global__ void __launch_bounds__(256, TR == 1 ? 4 : (kMath == 2 ? RTK_WFB_REF_W
         if (valid) {
             Ray ray = ray_init(F3{q.a.y, q.a.z, q.a.w}, F3{q.b.x, q.b.y, q.b.z});
             Stack st;
-            st.lds = &s_stack[wave][0][lane];
+            st.lds = &s_stack[wave][rtk::kLdsGuard][lane];
             st.glb = O.gstack + pix;
             st.gstride = O.local_pixels;
             st.fc = TR == 1 ? &s_fc[threadIdx.x] : TR == 2 ? &s_fc[wave * rtk::kTlWords] : nullptr;

@@ -64,9 +64,6 @@
 #ifndef RTK_FBN_REF_WAVES
 #define RTK_FBN_REF_WAVES 8 // waves per SIMD the S_ref depth > 1 first-bounce kernel is bounded to
 #endif
-#ifndef RTK_SEL_NEXT
-#define RTK_SEL_NEXT 0      // offset select (SEL) in the depth > 1 first-bounce kernel too
-#endif
 #ifndef RTK_WFB_REF_WAVES
 #define RTK_WFB_REF_WAVES 8 // waves per SIMD the S_ref bounce kernel is bounded to
 #endif
@@ -84,14 +81,6 @@
                             // around the launch (C2 0.0747 vs 0.0764 ms, rt_render into pageable memory 0.527
                             // vs 0.548 ms; C3, C5 equal: profiles/r05/ab/ext_events_ab.log)
 #endif
-#ifndef RTK_SHADE_EXP
-#define RTK_SHADE_EXP 0     // A/B experiments on the shading fetch only (2: none; pixels wrong)
-#endif
-#ifndef RTK_FAST_ENTRY
-#define RTK_FAST_ENTRY 0    // 1: frame kernels' entry without vector loads (the block's tile through the
-                            // scalar cache, the block size a constant): wave set-up 6.4 vs 7.3 us, but C3 /
-                            // C5 equal and C2 0.0757 vs 0.0747 ms (profiles/r05/ab/fast_entry_ab.log)
-#endif
 #ifndef RTK_LDS_STACK
 #define RTK_LDS_STACK 16    // LDS part of the traversal stack (C3 peaks at 9; deeper rays restart)
 #endif
@@ -108,6 +97,13 @@ using rtrec::kLeafBit;
 using rtrec::kRefError;
 constexpr int kLdsStack = RTK_LDS_STACK;
 constexpr int kGlobalStack = 64 - kLdsStack;         // slots kLdsStack..63
+// Rows of a lane's LDS column below entry 0.  The fast traversal (traverse_ifif) writes slot
+// sc - 2 and reads slot sc - 3 on every trip, whatever they hold; at stack counts 1 and 2 those
+// are rows -1 and -2, which exist so that neither address needs a clamp.  No row is needed above:
+// a trip starts with sc <= kLdsStack + 1 (a deeper stack has left the loop), so the highest row it
+// writes is entry kLdsStack - 1.  18 KiB per block: 8 blocks fit a CU's 160 KiB.
+constexpr int kLdsGuard = 2;
+constexpr int kLdsRows = kLdsGuard + kLdsStack;
 constexpr uint32_t kBlockPx = 16;                    // a block = 2 x 2 tiles of 8 x 8 pixels
 constexpr uint32_t kBlockThreads = 256;              // every frame kernel's block: 4 waves, one tile each
 
@@ -142,7 +138,6 @@ struct Frame {
     uint32_t* done;               // blocks finished so far (the last one builds lpt_next)
     uint32_t* zero_next;          // the other parity's frame counters, zeroed by this frame
     uint32_t nzero;
-    uint32_t* t0;                 // the launch's start (block 0's s_memrealtime), for RTK_LPT_BIAS
 };
 
 // A ray in flight between bounces: {pix, o.xyz}, {d.xyz, shadow_sum}, {colour.xyz, 3 * triangle it leaves from}.
@@ -263,7 +258,7 @@ __device__ __forceinline__ void leaf_bytes(const DevScene& S, uint32_t ref, uint
 }
 
 struct Stack {
-    uint32_t* lds;      // this lane's column: lds[i * 64]
+    uint32_t* lds;      // this lane's column: lds[i * 64], i >= -kLdsGuard
     uint32_t* glb;      // this pixel's column: glb[(i - kLdsStack) * gstride]
     uint64_t gstride;
     uint32_t* fc = nullptr;       // measurement instantiation: this lane's 8 fetch counters (LDS, stride 256)
@@ -334,14 +329,6 @@ __device__ __forceinline__ uint32_t frame_row(const Frame& F, uint32_t lr) {
 // (the trip's memory wait), [10] / [11] those trips' count whose wait was >= kTlLongWait ticks;
 // trips counted and times taken by the wave's first active lane.  (In a persistent bounce wave:
 // trips over all its groups, times of its last.)
-// inner_step's box test as n <= min(f, tHit) && f >= kTmin (1, default) instead of three compares
-// and two mask ANDs (0): same result for every input (rt_kernel_body.inc); the main loop issues two
-// SALU instructions fewer per trip.  C2 0.0587 vs 0.0603 ms per frame, C3 0.2914 vs 0.2978, C4
-// 1.046 vs 1.073 (three runs each, profiles/r06/ab_imin/table.txt); the bound as a NaN-sentinel
-// select instead (folding f >= kTmin in as well) made the loop 10 instructions longer
-#ifndef RTK_IMIN
-#define RTK_IMIN 1
-#endif
 #ifndef RTK_TL_SPLIT
 #define RTK_TL_SPLIT 0
 #endif
@@ -379,19 +366,9 @@ __device__ __forceinline__ void timeline_store(const Outputs& O, uint32_t w, uin
     }
 }
 
-// The block's tile.  A uniform address: read through the scalar cache (RTK_FAST_ENTRY), not as a
-// vector load that would queue behind the traversal requests of the waves already running on the
-// CU.  The table is never written while a launch that reads it runs, except by that launch's
-// last block (the next frame's longest-first order), after every block has read its entry; the
-// next launch starts with the scalar cache invalidated.
-__device__ __forceinline__ uint32_t block_tile(const Frame& F) {
-#if RTK_FAST_ENTRY
-    typedef const __attribute__((address_space(4))) uint32_t cu32;
-    return *((cu32*)F.tile_order + blockIdx.x);
-#else
-    return F.tile_order[blockIdx.x];
-#endif
-}
+// The block's tile.  (Read through the scalar cache instead, with the block size a constant, the
+// wave set-up took 6.4 vs 7.3 us, but no config gained: DESIGN.md 7.5.)
+__device__ __forceinline__ uint32_t block_tile(const Frame& F) { return F.tile_order[blockIdx.x]; }
 
 // Lane -> pixel inside a block's 16x16 pixels: wave w holds 8x8 tile (w % 2, w / 2), lanes
 // in Morton order.  The vector-memory path merges the requests of the four lanes of a quad
@@ -410,11 +387,7 @@ __device__ __forceinline__ void tile_pixel(const Frame& F, uint32_t tb, int wave
 // other one for frame f + 1 on the same stream (the kernels of f never touch it), so no
 // launch is spent on zeroing.
 __device__ __forceinline__ void zero_next_counters(const Frame& F) {
-#if RTK_FAST_ENTRY
-    const uint32_t bd = kBlockThreads;   // blockDim.x is a load from the dispatch packet
-#else
     const uint32_t bd = blockDim.x;
-#endif
     const uint32_t n = gridDim.x * bd;
     for (uint32_t i = blockIdx.x * bd + threadIdx.x; i < F.nzero; i += n) F.zero_next[i] = 0u;
 }
@@ -474,13 +447,6 @@ __device__ __forceinline__ uint32_t lpt_key(uint32_t c) {
 #ifndef RTK_LPT_VEC
 #define RTK_LPT_VEC 1
 #endif
-#ifndef RTK_LPT_BIAS
-#define RTK_LPT_BIAS 0      // > 0: a block's cost for the next frame's order adds its start offset in the
-                            // launch >> RTK_LPT_BIAS (blocks that ran late measured shorter, same work)
-#endif
-#ifndef RTK_EPI_NOWAIT
-#define RTK_EPI_NOWAIT 0   // 1: the cost store and the counter add in flight together (profiles/r05/ab/epi_nowait_ab.log: equal)
-#endif
 constexpr int kEpilogueWords = 8 + 256 + 2 * 256;   // wave times + flag, histogram, two scan rows
 static_assert(4 * kLdsStack * 64 >= kEpilogueWords, "tile_epilogue's scratch must fit the blocks' traversal stacks");
 constexpr uint32_t kKeyBytes = (4u * kLdsStack * 64u - (uint32_t)kEpilogueWords) * 4u;
@@ -497,12 +463,6 @@ __device__ __forceinline__ void load_costs16(const uint32_t* cost, uint32_t q0, 
     // the wait "writes" the four results, so no use of them is scheduled above it
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]) : : "memory");
 }
-// RTK_LPT_BIAS: block 0 notes when the launch started (its first stamp; the frame's counter set
-// is zeroed before the frame, so 0 = not yet seen)
-__device__ __forceinline__ void note_launch_start(const Frame& F, uint32_t t_start) {
-    if (RTK_LPT_BIAS && F.tile_cost && blockIdx.x == 0 && threadIdx.x == 0)
-        __hip_atomic_store(F.t0, t_start, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ void tile_epilogue(const Frame& F, uint32_t tb, uint32_t t_start, uint32_t* scratch) {
     if (!F.tile_cost) return;   // launch-uniform
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
@@ -511,20 +471,11 @@ __device__ void tile_epilogue(const Frame& F, uint32_t tb, uint32_t t_start, uin
     if (lane == 0) scratch[wave] = t_end - t_start + 1u;
     __syncthreads();
     if (tid == 0) {
-        uint32_t c = max(max(scratch[0], scratch[1]), max(scratch[2], scratch[3]));
-        if (RTK_LPT_BIAS) {
-            const uint32_t T0 = __hip_atomic_load(F.t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t off = t_start - T0;
-            if (T0 != 0u && off < (1u << 26)) c += off >> RTK_LPT_BIAS;
-        }
+        const uint32_t c = max(max(scratch[0], scratch[1]), max(scratch[2], scratch[3]));
         __hip_atomic_store(F.tile_cost + tb, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // RTK_EPI_NOWAIT: where the last block reads every cost exactly once (the keys kept in
-        // LDS), the add does not wait for the store: the store and the add are in flight together
-        // (one round trip per block instead of two), and a cost that lands after the last block
-        // read it leaves the previous frame's cost of that block in this sort -- a key of the
-        // schedule, never of a pixel: the order is a permutation of the blocks either way.
-        // Grids read twice (past kKeyBytes blocks) need every cost stable between the passes.
-        if (!RTK_EPI_NOWAIT || !RTK_LPT_VEC || gridDim.x > kKeyBytes) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // the cost has landed before the block counts itself done: the last block reads every cost
+        // (letting the store and the add fly together measured equal: DESIGN.md 7.5)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         const uint32_t prev = __hip_atomic_fetch_add(F.done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         scratch[4] = prev + 1u == gridDim.x ? 1u : 0u;
     }
@@ -1183,8 +1134,7 @@ static hipError_t wait_ctx(rt_ctx* c, hipStream_t s) {
 // bounce kernel (rtk::grab_group)
 constexpr size_t kBounceWords = 32 + rtk::kCursorSet;
 constexpr size_t kRestartSlot = kBounceWords * (RT_MAX_DEPTH + 1);
-constexpr size_t kT0Slot = kRestartSlot + 1;   // the launch's start (RTK_LPT_BIAS)
-constexpr size_t kCounters = kRestartSlot + 2;
+constexpr size_t kCounters = kRestartSlot + 1;
 
 static int set_err(rt_ctx* c, const std::string& m, int code) {
     if (c) c->err = m; else { g_err = m; rtrefit::clear_error(); }
@@ -2336,7 +2286,6 @@ static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint3
     F.nzero = (uint32_t)L.wcnt_set;   // all of it: the next frame may be deeper than this one
     auto sums = [&](int k) { return cnt + kCounters + (size_t)(k - 1) * (nchunk + nsuper); };   // queue k >= 1
     O.restarts = cnt + kRestartSlot;
-    F.t0 = cnt + kT0Slot;
 
     // static block order: a host-built table per block grid, made once (a new table goes into
     // a new allocation, so frames in flight that read another grid's table never wait)
