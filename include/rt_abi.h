@@ -485,6 +485,13 @@ int rt_timing_average(rt_ctx* ctx, int32_t n, float* total_ms, float* traverse_m
  * SIMD on every CU reads pseudo-random inner-record-shaped records from a table of
  * table_records 64-B records, iters (multiple of 4) per lane: ms per launch and records read. */
 int rt_fetch_counts(rt_ctx* ctx, uint32_t w, uint32_t h, int32_t depth, uint32_t flags, uint64_t* out8);
+/* rt_loop_variant_counts renders one frame the same way (RT_FLAG_EXACT_DIV allowed) and returns
+ * which copy of the fast traversal's loop each wave's traversals took: out[0] = closest-hit
+ * traversals through the generic loop (any math form), out[1 + k] = through the loop of octant k
+ * (bit 0 / 1 / 2 of k set: the x / y / z direction component of every active ray is negative;
+ * taken when no active ray has a zero component and their signs agree), out[9] and out[10 + k]
+ * the same for the any-hit (shadow) traversals.  A traversal of a wave counts once. */
+int rt_loop_variant_counts(rt_ctx* ctx, uint32_t w, uint32_t h, int32_t depth, uint32_t flags, uint64_t* out18);
 int rt_gather_peak(rt_ctx* ctx, uint32_t table_records, uint32_t iters, float* ms, uint64_t* records);
 /* rt_chase_peak measures the other roof, latency: every wave of 8 per SIMD on every CU walks
  * a chain of `iters` dependent traversal-shaped iterations (three 16-B + one 8-B load of a

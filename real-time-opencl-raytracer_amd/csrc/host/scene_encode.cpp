@@ -125,6 +125,11 @@ int encode_scene(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t
                 const float a = std::fabs(qf[j]);
                 if (!(a == 0.0f || (a >= 0x1p-66f && a <= 0x1p60f))) fast_ok = false;
             }
+            // the octant loops (slab2_pk's OCT) name near and far by the ray's sign: both children's
+            // min <= max.  An inverted box sends the scene to the division form, as a coordinate
+            // outside the domain does.  (The device builds, rt_refit.hip and rt_scene_build.hip,
+            // make every box as min / max over finite data, so theirs are ordered.)
+            if (!(qf[0] <= qf[2] && qf[1] <= qf[3])) fast_ok = false;
         }
     }
     // triangle reference records {v0|id, e1, e2} (volumeRender.cl:965-974), layout of tri_rec

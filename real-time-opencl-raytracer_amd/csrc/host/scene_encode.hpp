@@ -19,7 +19,7 @@ struct EncodedScene {
     std::vector<int32_t> inner_id;   // node -> the id of its inner record, -1: none (rtrefit::plan_build)
     uint32_t root = 0;               // the root's reference
     uint32_t n_inner = 0;
-    int fast_div = 0;                // every box coordinate is 0 or in [2^-66, 2^60]
+    int fast_div = 0;                // every box coordinate is 0 or in [2^-66, 2^60], every child box min <= max
     int clean = 0;                   // no reachable malformed inner node (kRefError)
 };
 

@@ -39,7 +39,8 @@ __device__ __forceinline__ float xdiv(float a, float d, float y) {
     return __builtin_fmaf(r, y, q);
 }
 // Numerators are (box - o): when |o| and every box coordinate are 0 or in
-// [2^-66, 2^60] (the box side is checked at upload -> S.fast_div), both are
+// [2^-66, 2^60] (the box side is checked at upload -> S.fast_div, which also says that
+// every child box has min <= max on every axis: the octant loops' precondition), both are
 // multiples of 2^-89, so a non-zero difference is >= 2^-89 and <= 2^61.
 __device__ __forceinline__ bool axis_ok(float o, float d) {
     const float ad = fabsf(d), ao = fabsf(o);
@@ -116,7 +117,15 @@ __device__ __forceinline__ RayPk ray_pk(const F3& o, const F3& d, const F3& y) {
     return RayPk{v2f{ox, oy}, v2f{oz, dz}, v2f{yx, yy}, v2f{dx, dy}, v2f{yz, yz}, d.x == 0.0f, d.y == 0.0f,
                  d.z == 0.0f};
 }
-template <bool ZERO = true>
+// OCT -1: near and far picked per lane by the min/max network.  OCT 0..7 (bit k set: direction
+// component k is negative in every lane of the wave, and none is +-0; traverse_fast): near and far
+// are known by name.  On an axis with box.min <= box.max (checked at upload -> S.fast_div) the
+// subtraction of a common o and the multiplication by a common y -- or the correctly rounded
+// quotient by a common d -- are monotone and give no NaN inside the fast quotient's domain, so
+// d > 0 orders the two slab values as the box's planes and d < 0 the other way round: min(a, b) is
+// a or b itself, and n and f are one v_max3 / v_min3 each, 4 VALU per visit instead of 16.  Which
+// of two equal values comes out (+-0 included) may differ; everything downstream only compares.
+template <bool ZERO = true, int OCT = -1>
 __device__ __forceinline__ void slab2_pk(const float4& q0, const float4& q1, const float4& q2, const RayPk& R,
                                          float& n0, float& f0, float& n1, float& f1) {
     // x: o, d, y = lo halves of R.oxy / R.dxy / R.yxy; y: the hi halves; z: lo / hi of R.ozdz, lo of R.yz
@@ -141,6 +150,17 @@ __device__ __forceinline__ void slab2_pk(const float4& q0, const float4& q1, con
             ay = pk_pick(R.zy, ay, m2); by = pk_pick(R.zy, by, m3);
             az = pk_pick(R.zz, az, m4); bz = pk_pick(R.zz, bz, m5);
         }
+    }
+    if (OCT >= 0) {
+        static_assert(OCT < 0 || !ZERO, "an octant loop has no zero direction component");
+        const v2f nx = (OCT & 1) ? bx : ax, fx = (OCT & 1) ? ax : bx;
+        const v2f ny = (OCT & 2) ? by : ay, fy = (OCT & 2) ? ay : by;
+        const v2f nz = (OCT & 4) ? bz : az, fz = (OCT & 4) ? az : bz;
+        n0 = max3_(nx.x, ny.x, nz.x);
+        f0 = min3_(fx.x, fy.x, fz.x);
+        n1 = max3_(nx.y, ny.y, nz.y);
+        f1 = min3_(fx.y, fy.y, fz.y);
+        return;
     }
     // v_min/v_max return the other operand for a NaN input, as fmin/fmax (a NaN only
     // arises for a zero direction component); the nesting is the reference's.  asm
@@ -285,6 +305,7 @@ __device__ int traverse(const DevScene& S, const Ray& ray, float& tHit, const St
 // MODE 0: packed fast quotient; 1: + Markstein's zero-direction select (S_strict / S_hw
 // only); 2: the division form (a ray outside the fast quotient's domain).
 // ---------------------------------------------------------------------------
+constexpr bool kOctLoops = kMath == 2;
 constexpr uint32_t kStackBase = 0x80000000u - (uint32_t)(kLdsStack + 1) * 256u, kStackDone = 0u;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 __device__ __forceinline__ uint32_t lds_get(int a) { return *(lds_u32*)(uintptr_t)(uint32_t)a; }
@@ -301,7 +322,7 @@ template <bool GUARD> __device__ __forceinline__ int slot_put(int get_at, int co
 }
 
 // put_at: the LDS address of slot sc - 2
-template <int MODE>
+template <int MODE, int OCT = -1>
 __device__ __forceinline__ void inner_step(const float4& q0, const float4& q1, const float4& q2, float2 refs,
                                            const RayPk& rp, float th, uint32_t popped, int put_at,
                                            uint32_t& cur, uint32_t& nxt, uint32_t& sb) {
@@ -309,7 +330,7 @@ __device__ __forceinline__ void inner_step(const float4& q0, const float4& q1, c
     if (MODE == 2) {
         slab2_div(q0, q1, q2, F3{rp.oxy.x, rp.oxy.y, rp.ozdz.x}, F3{rp.dxy.x, rp.dxy.y, rp.ozdz.y}, n0, f0, n1, f1);
     } else {
-        slab2_pk<MODE == 1>(q0, q1, q2, rp, n0, f0, n1, f1);
+        slab2_pk<MODE == 1, MODE == 0 ? OCT : -1>(q0, q1, q2, rp, n0, f0, n1, f1);
     }
     // (n <= f) && (n <= th) == n <= min(f, th) for every input: th is a finite hit distance, and n
     // and f are NaN together or not at all (per axis the NaN-ignoring min and max of the two slab
@@ -351,7 +372,7 @@ __device__ __forceinline__ float2 rec_load2(__amdgpu_buffer_rsrc_t r, uint32_t o
     return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
 }
 
-template <bool CLOSEST, int MODE, int TR, bool SEL = false, bool GUARD = true>
+template <bool CLOSEST, int MODE, int TR, bool SEL = false, bool GUARD = true, int OCT = -1>
 __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, float& tHit, const Stack& st,
                                               int& result) {
     const int col0 = (int)(uint32_t)(uintptr_t)(lds_u32*)st.lds;   // the column's entry 0, as an LDS byte address
@@ -399,7 +420,7 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
         const float4 q1 = make_float4(__uint_as_float(u1.x), __uint_as_float(u1.y), __uint_as_float(u1.z), __uint_as_float(u1.w));
         const float4 q2 = make_float4(__uint_as_float(u2.x), __uint_as_float(u2.y), __uint_as_float(u2.z), __uint_as_float(u2.w));
         const float2 q3 = make_float2(__uint_as_float(u3.x), __uint_as_float(u3.y));
-        inner_step<MODE>(q0, q1, q2, q3, rp, th, popped, slot_put<GUARD>(at, col0, sb), cur, nxt, sb);
+        inner_step<MODE, OCT>(q0, q1, q2, q3, rp, th, popped, slot_put<GUARD>(at, col0, sb), cur, nxt, sb);
     }
     if (TR == 2 && CLOSEST) rtk::timeline_mark(st.fc, 7);   // its wave-uniform prologue is over
     while ((int)sb >= (int)kStackBase) {
@@ -436,7 +457,7 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
             rtk::timeline_wait(st.fc, CLOSEST ? 0 : 1, (uint32_t)__builtin_amdgcn_s_memrealtime() - t_issue);
         }
         if (!leaf) {
-            inner_step<MODE>(q0, q1, q2, q3, rp, th, popped, slot_put<GUARD>(at, col0, sb), cur, nxt, sb);
+            inner_step<MODE, OCT>(q0, q1, q2, q3, rp, th, popped, slot_put<GUARD>(at, col0, sb), cur, nxt, sb);
         } else {
             // Moller-Trumbore on one reference of the leaf, in order (:965-997).  An empty leaf
             // (tk == tend) tests the record after its range (in the allocation, or zeros) and
@@ -463,26 +484,75 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
 // Markstein's zero-direction select costs 12 VALU per visit and is needed by ~1e-5 of
 // rays, the division form by fewer still: a wave runs those variants only when one of
 // its rays needs them (wave-uniform branch, one code copy each).
-template <bool CLOSEST, int TR, bool SEL = false, bool GUARD = true>
+//
+// Octant loops (slab2_pk's OCT): when no active lane has a zero direction component and each
+// component's sign is the same in all of them -- an 8x8 tile's primary rays, or its shadow rays
+// toward the one light, unless the tile straddles a zero of a component -- the wave runs the copy
+// of the MODE 0 loop compiled for that octant, 12 VALU per inner visit shorter.  The choice is
+// made here, once per traversal, by ballots over the active lanes; the loops themselves gain
+// nothing.  Every other wave runs the generic MODE 0 loop, as before.
+// OCTS: the kernel has the octant loops.  Those are S_ref's depth-1 kernels (kOctLoops and SEL:
+// first_bounce_kernel and first_bounce_batch_kernel without NEXT), which stay within 64 VGPRs with no
+// scratch.  With nine copies of the loop the register allocator gave every other kernel more
+// scratch than it has (S_strict / S_hw first-bounce 0 -> 8 B, S_hw render_kernel 104 -> 120 B, S_ref
+// render_kernel 28 -> 40 B, wf_bounce_kernel 24 -> 32 B, the depth > 1 batch kernel 0 -> 8 B), so
+// they keep the generic loop alone.
+// TR 1 (rt_loop_variant_counts): the loop a wave's traversal took, counted in st.vc[0] (generic;
+// MODE 1 and 2 too) or st.vc[1 + octant], closest-hit traversals first, any-hit ones 9 further.
+template <bool CLOSEST, int TR>
+__device__ __forceinline__ void variant_count(const Stack& st, int which) {
+    if (TR == 1 && (uint32_t)(threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec()))
+        atomicAdd(st.vc + (CLOSEST ? 0 : 9) + which, 1ull);
+}
+template <bool CLOSEST, int TR, bool SEL = false, bool GUARD = true, bool OCTS = false>
 __device__ __forceinline__ bool traverse_fast(const DevScene& S, Ray& ray, float& tHit, const Stack& st,
                                               int& result) {
-    if (!S.fast_div || __builtin_amdgcn_ballot_w64(!fast_div_ok(ray)))
+    if (!S.fast_div || __builtin_amdgcn_ballot_w64(!fast_div_ok(ray))) {
+        variant_count<CLOSEST, TR>(st, 0);
         return traverse_ifif<CLOSEST, 2, TR, SEL, GUARD>(S, ray, tHit, st, result);
+    }
     if (kMath != 2) {
         const bool z = ray.dir.x == 0.0f || ray.dir.y == 0.0f || ray.dir.z == 0.0f;
-        if (__builtin_amdgcn_ballot_w64(z)) return traverse_ifif<CLOSEST, 1, TR, SEL, GUARD>(S, ray, tHit, st, result);
+        if (__builtin_amdgcn_ballot_w64(z)) {
+            variant_count<CLOSEST, TR>(st, 0);
+            return traverse_ifif<CLOSEST, 1, TR, SEL, GUARD>(S, ray, tHit, st, result);
+        }
     }
+    if (OCTS) {
+        // S_ref's MODE 0 also serves zero components (see slab2_pk), hence the zero test here; no lane
+        // has a NaN (fast_div_ok), so d < 0 is the sign bit of a non-zero d
+        const bool z = ray.dir.x == 0.0f || ray.dir.y == 0.0f || ray.dir.z == 0.0f;
+        const uint64_t act = __builtin_amdgcn_read_exec();
+        const uint64_t sx = __builtin_amdgcn_ballot_w64(ray.dir.x < 0.0f), sy = __builtin_amdgcn_ballot_w64(ray.dir.y < 0.0f),
+                       sz = __builtin_amdgcn_ballot_w64(ray.dir.z < 0.0f);
+        const bool uniform = (sx == 0 || sx == act) && (sy == 0 || sy == act) && (sz == 0 || sz == act);
+        const int oct = (sx ? 1 : 0) | (sy ? 2 : 0) | (sz ? 4 : 0);
+        if (__builtin_amdgcn_ballot_w64(z) == 0 && uniform) {
+            variant_count<CLOSEST, TR>(st, 1 + oct);
+            switch (oct) {
+                case 0: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 0>(S, ray, tHit, st, result);
+                case 1: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 1>(S, ray, tHit, st, result);
+                case 2: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 2>(S, ray, tHit, st, result);
+                case 3: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 3>(S, ray, tHit, st, result);
+                case 4: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 4>(S, ray, tHit, st, result);
+                case 5: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 5>(S, ray, tHit, st, result);
+                case 6: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 6>(S, ray, tHit, st, result);
+                default: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 7>(S, ray, tHit, st, result);
+            }
+        }
+    }
+    variant_count<CLOSEST, TR>(st, 0);
     return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD>(S, ray, tHit, st, result);
 }
 
 // Closest-hit / any-hit of one ray: the fast traversal, restarted with the general
 // code when its stack outgrows the LDS part (counted in O.restarts).
-template <bool CLOSEST, bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true>
+template <bool CLOSEST, bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true, bool OCTS = false>
 __device__ __forceinline__ int trace(const DevScene& S, const Outputs& O, Ray& ray, float& t, const Stack& st,
                                      bool& overflow) {
     int hit;
     if (FASTONLY) {
-        if (traverse_fast<CLOSEST, TR, SEL, GUARD>(S, ray, t, st, hit)) return hit;
+        if (traverse_fast<CLOSEST, TR, SEL, GUARD, OCTS>(S, ray, t, st, hit)) return hit;
         atomicAdd(O.restarts, 1u);
         t = 4294967296.0f;
     }
@@ -546,12 +616,12 @@ __device__ __forceinline__ void park_next(const F3& dir, const F3& normal, const
 }
 
 // Shadow ray from a hit (volumeRender.cl:1437-1460): any-hit, shadowed iff hit && t > 0.025.
-template <bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true>
+template <bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true, bool OCTS = false>
 __device__ __forceinline__ float shadow_coef(const DevScene& S, const Outputs& O, const F3& hitpoint, const F3& L,
                                              const Stack& st, bool& overflow, int& sh) {
     Ray sray = ray_init(mad3(L, 0.001f, hitpoint), L);   // hitpoint + L * 0.001f
     float ts = 4294967296.0f;
-    sh = trace<false, FASTONLY, TR, SEL, GUARD>(S, O, sray, ts, st, overflow);
+    sh = trace<false, FASTONLY, TR, SEL, GUARD, OCTS>(S, O, sray, ts, st, overflow);
     return (sh >= 0 && ts > 0.025f) ? 0.25f : 1.0f;
 }
 
@@ -668,13 +738,13 @@ enum { kFinishMiss = 0, kFinishHit = 1, kContinue = 2 };
 // only the shadow sum is stored after the shadow trace, so nothing is parked across that
 // trace (no LDS for the next ray).  `color += rez` before the shadow trace is the same
 // float op on the same operands as after it (volumeRender.cl:1483).
-template <bool FASTONLY, int TR = 0, bool SEL = false>
+template <bool FASTONLY, int TR = 0, bool SEL = false, bool OCTS = false>
 __device__ __forceinline__ int wf_bounce(const DevScene& S, const Frame& F, const Outputs& O, const WQ& W,
                                          int want_aux, uint32_t pix, int k, Ray ray, F3& color, float& ss,
                                          const Stack& st, bool& overflow) {
     const int depth = F.depth;
     float tHit = 4294967296.0f;
-    const int hit = trace<true, FASTONLY, TR, SEL>(S, O, ray, tHit, st, overflow);
+    const int hit = trace<true, FASTONLY, TR, SEL, true, OCTS>(S, O, ray, tHit, st, overflow);
     if (TR == 2) rtk::timeline_mark(st.fc, 4);   // the closest-hit traversal is done
     if (want_aux) {
         O.hits[((size_t)pix * depth + k) * 2] = hit;
@@ -700,7 +770,7 @@ __device__ __forceinline__ int wf_bounce(const DevScene& S, const Frame& F, cons
     float coef = 1.0f;
     if (!(F.flags & RT_FLAG_NO_SHADOW)) {
         int sh;
-        coef = shadow_coef<FASTONLY, TR, SEL>(S, O, hitpoint, L, st, overflow, sh);
+        coef = shadow_coef<FASTONLY, TR, SEL, true, OCTS>(S, O, hitpoint, L, st, overflow, sh);
         if (want_aux) O.hits[((size_t)pix * depth + k) * 2 + 1] = sh;
     }
     ss += coef;
@@ -754,7 +824,8 @@ __device__ __forceinline__ void first_bounce_pixel(const DevScene& S, const Fram
             st.glb = O.gstack + pix;
             st.gstride = O.local_pixels;
             st.fc = fc;
-            const int r = wf_bounce<FASTONLY, TR, SEL>(S, F, O, W, want_aux, pix + qbase, 0, ray, color, ss, st, overflow);
+            if (TR == 1) st.vc = O.fcount + rtk::kFetchCounts;
+            const int r = wf_bounce<FASTONLY, TR, SEL, kOctLoops && SEL>(S, F, O, W, want_aux, pix + qbase, 0, ray, color, ss, st, overflow);
             if (r != kContinue) wf_finish(O, want_aux, pix, oi, color, ss, r == kFinishHit ? 1 : 0);
         }
     }
@@ -763,8 +834,8 @@ __device__ __forceinline__ void first_bounce_pixel(const DevScene& S, const Fram
 
 // Bounce 0, one lane per pixel, one wave per 8x8 tile (the reference's work-group),
 // four tiles per block; continuing rays go to W.out.  At depth 1 this is the whole
-// frame: without the bounce loop it fits 8 waves per SIMD in S_ref (59 VGPRs, no scratch), and its
-// traversal computes record offsets without a branch (SEL).
+// frame: without the bounce loop it fits 8 waves per SIMD in S_ref (62 VGPRs, no scratch), its
+// traversal computes record offsets without a branch (SEL), and in S_ref it has the octant loops (OCTS).
 // NEXT (depth > 1): continuing rays are appended to W.out, wave w of tile tb to segment
 // 4 tb + w (screen order).
 // TR 1: the measurement instantiation (rt_fetch_counts) that counts every fetch; TR 2: the
@@ -905,6 +976,7 @@ __global__ void __launch_bounds__(256, TR == 1 ? 4 : (kMath == 2 ? RTK_WFB_REF_W
             st.glb = O.gstack + pix;
             st.gstride = O.local_pixels;
             st.fc = TR == 1 ? &s_fc[threadIdx.x] : TR == 2 ? &s_fc[wave * rtk::kTlWords] : nullptr;
+            if (TR == 1) st.vc = O.fcount + rtk::kFetchCounts;
             const int r = wf_bounce<FASTONLY, TR>(S, F, O, Wg, want_aux, pix, k, ray, color, ss, st, overflow);
             if (r != kContinue) wf_finish(O, want_aux, pix, pix, color, ss, r == kFinishHit ? k + 1 : k);
         }

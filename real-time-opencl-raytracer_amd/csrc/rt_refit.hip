@@ -123,6 +123,10 @@ __device__ __forceinline__ void refit_record(const DevArgs& A, uint32_t id, bool
     for (int k = 0; k < 3; ++k) {
         rec[k] = make_float4(mnL[k], mnR[k], mxL[k], mxR[k]);   // axis-major, as the upload lays it out
         ok = ok && coord_ok(mnL[k]) && coord_ok(mnR[k]) && coord_ok(mxL[k]) && coord_ok(mxR[k]);
+        // S.fast_div also promises min <= max (the octant loops, rt_kernel_body.inc slab2_pk).  A box
+        // made here is min / max over finite data (a NaN fails coord_ok), hence ordered; only an
+        // empty leaf's box, kept as uploaded, can be inverted
+        ok = ok && mnL[k] <= mxL[k] && mnR[k] <= mxR[k];
     }
     if (!ok) A.out[0] = 0u;
     if (is_root) {

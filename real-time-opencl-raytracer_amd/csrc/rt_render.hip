@@ -116,7 +116,7 @@ struct DevScene {
     uint32_t rec_bytes;                  // bytes of that allocation
     uint32_t root;
     uint32_t n_inner;                    // inner records; the first ones are the BVH's top levels (BFS order)
-    int fast_div;                        // every box coordinate is 0 or in [2^-66, 2^60]
+    int fast_div;                        // every box coordinate is 0 or in [2^-66, 2^60], every child box min <= max
     int clean;                           // no reachable malformed inner node (kRefError)
 };
 
@@ -214,7 +214,8 @@ struct Outputs {
     unsigned long long* overflow;
     uint32_t* restarts;          // traversals that outgrew the LDS stack and restarted (general code)
     uint64_t local_pixels;
-    // measurement instantiation only (rt_fetch_counts): the frame's 8 record-fetch counters
+    // measurement instantiation only (rt_fetch_counts, rt_loop_variant_counts): the frame's 8
+    // record-fetch counters, then its kVariantCounts loop-variant counters
     unsigned long long* fcount;
     // depth-1 kernel only: out is the whole w x h frame (rt_render_tiled: every context writes
     // its bands' pixels straight into their rows of one frame); 0: out holds this rank's bands
@@ -262,6 +263,7 @@ struct Stack {
     uint32_t* glb;      // this pixel's column: glb[(i - kLdsStack) * gstride]
     uint64_t gstride;
     uint32_t* fc = nullptr;       // measurement instantiation: this lane's 8 fetch counters (LDS, stride 256)
+    unsigned long long* vc = nullptr;   // measurement instantiation: the frame's 18 loop-variant counters (traverse_fast)
     __device__ __forceinline__ uint32_t get(int i) const {
         return i < kLdsStack ? lds[i * 64] : glb[(uint64_t)(i - kLdsStack) * gstride];
     }
@@ -281,6 +283,10 @@ struct Stack {
 // wave-distinct, [6] wave iterations, [7] mixed iterations; stride 256 (one block's lanes).
 // vmem = false: a record the wave read once through the scalar cache (the traversal's
 // wave-uniform prologue): a lane fetch and a wave-distinct record, but no quad request.
+// After the 8 fetch counters O.fcount holds the frame's loop-variant counters (rt_loop_variant_counts,
+// rt_kernel_body.inc traverse_fast): wave traversals through the generic loop and the 8 octant loops,
+// closest-hit then any-hit.
+constexpr int kFetchCounts = 8, kVariantCounts = 18;
 __device__ __forceinline__ void fetch_count(uint32_t* fc, bool leaf, uint32_t id, bool vmem = true) {
     const uint64_t act = __builtin_amdgcn_read_exec();
     const int lane = (int)(threadIdx.x & 63u);
@@ -2693,19 +2699,24 @@ int rt_last_deferred(rt_ctx* c, uint32_t* count) {
     return RT_OK;
 }
 
-int rt_fetch_counts(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint32_t flags, uint64_t* out8) {
-    if (!c || !out8 || w == 0 || h == 0 || depth < 1 || depth > RT_MAX_DEPTH)
-        return set_err(c, "rt_fetch_counts: invalid argument", RT_ERR_INVALID_ARG);
-    if ((depth > 1 && !(flags & RT_FLAG_WAVEFRONT)) || (flags & RT_FLAG_EXACT_DIV) || !c->have_scene || !c->scene.clean ||
-        c->scene.split)
-        return set_err(c, "rt_fetch_counts: the fast kernels of a clean scene, depth 1 or the wavefront path",
+// One frame through the counting instantiation (TR == 1) of the fast kernels: its 8 fetch counters
+// (out8) and its loop-variant counters (out18), either may be null.
+static int counted_frame(rt_ctx* c, const char* who, uint32_t w, uint32_t h, int32_t depth, uint32_t flags, uint64_t* out8,
+                         uint64_t* out18) {
+    constexpr int kN = rtk::kFetchCounts + rtk::kVariantCounts;
+    if (!c || (!out8 && !out18) || w == 0 || h == 0 || depth < 1 || depth > RT_MAX_DEPTH)
+        return set_err(c, std::string(who) + ": invalid argument", RT_ERR_INVALID_ARG);
+    // the fetch counters are about the fast quotient's loops; the variant counters also say what
+    // RT_FLAG_EXACT_DIV does (every traversal through the generic division form)
+    if ((depth > 1 && !(flags & RT_FLAG_WAVEFRONT)) || (out8 && (flags & RT_FLAG_EXACT_DIV)) || !c->have_scene || !c->scene.clean || c->scene.split)
+        return set_err(c, std::string(who) + ": the fast kernels of a clean scene, depth 1 or the wavefront path",
                        RT_ERR_INVALID_ARG);
     HIPC(c, hipSetDevice(c->device));
     int rc = ensure(c, c->d_out, c->out_cap, (size_t)w * h);
     if (rc) return rc;
     unsigned long long* d = nullptr;
-    HIPC(c, hipMalloc((void**)&d, 8 * sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(d, 0, 8 * sizeof(unsigned long long), c->stream);
+    HIPC(c, hipMalloc((void**)&d, kN * sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(d, 0, kN * sizeof(unsigned long long), c->stream);
     if (e == hipSuccess) {
         c->trace.on = true;
         c->trace.d_counts = d;
@@ -2713,14 +2724,25 @@ int rt_fetch_counts(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint32_t f
         c->trace.on = false;
         c->trace.d_counts = nullptr;
     }
-    unsigned long long hc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long hc[kN] = {};
     if (e == hipSuccess && rc == RT_OK) e = hipMemcpyAsync(hc, d, sizeof hc, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);
     if (rc) return rc;
-    if (e != hipSuccess) return set_err(c, std::string("rt_fetch_counts: ") + hipGetErrorString(e), RT_ERR_DEVICE);
-    for (int k = 0; k < 8; ++k) out8[k] = hc[k];
+    if (e != hipSuccess) return set_err(c, std::string(who) + ": " + hipGetErrorString(e), RT_ERR_DEVICE);
+    if (out8)
+        for (int k = 0; k < rtk::kFetchCounts; ++k) out8[k] = hc[k];
+    if (out18)
+        for (int k = 0; k < rtk::kVariantCounts; ++k) out18[k] = hc[rtk::kFetchCounts + k];
     return RT_OK;
+}
+
+int rt_fetch_counts(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint32_t flags, uint64_t* out8) {
+    return counted_frame(c, "rt_fetch_counts", w, h, depth, flags, out8, nullptr);
+}
+
+int rt_loop_variant_counts(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint32_t flags, uint64_t* out18) {
+    return counted_frame(c, "rt_loop_variant_counts", w, h, depth, flags, nullptr, out18);
 }
 
 int rt_gather_peak(rt_ctx* c, uint32_t table_records, uint32_t iters, float* ms, uint64_t* records) {

@@ -226,6 +226,9 @@ __global__ void __launch_bounds__(kThreads) inner_kernel(const float4* nodes, ui
     // axis-major: {L.min, R.min, L.max, R.max} per axis
     const float4 q[3] = {make_float4(lmn.x, rmn.x, lmx.x, rmx.x), make_float4(lmn.y, rmn.y, lmx.y, rmx.y),
                          make_float4(lmn.z, rmn.z, lmx.z, rmx.z)};
+    // S.fast_div also promises min <= max on every axis of every child box (the octant loops,
+    // rt_kernel_body.inc slab2_pk): the LBVH's boxes are min / max over at least one triangle's
+    // vertices, so a box of finite data is ordered, and a NaN fails coord_ok.
     bool ok = true;
     for (int k = 0; k < 3; ++k) {
         rec[k] = q[k];

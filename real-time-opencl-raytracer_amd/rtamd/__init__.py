@@ -92,7 +92,7 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_peer_access", "rt_frame_sync_words", "rt_bands_put_sync", "rt_frame_present", "rt_frame_release",
                "rt_frame_sync_status", "rt_frame_checksum", "rt_shared_alloc", "rt_shared_free", "rt_copy_device",
                "rt_scene_image_size", "rt_scene_image_pack",
-               "rt_scene_image_load", "rt_fetch_counts", "rt_gather_peak", "rt_chase_peak", "rt_chase_latency", "rt_wave_timeline", "rt_last_timing", "rt_timing_average", "rt_last_deferred", "rt_overflow_count", "rt_destroy", "rt_last_error",
+               "rt_scene_image_load", "rt_fetch_counts", "rt_loop_variant_counts", "rt_gather_peak", "rt_chase_peak", "rt_chase_latency", "rt_wave_timeline", "rt_last_timing", "rt_timing_average", "rt_last_deferred", "rt_overflow_count", "rt_destroy", "rt_last_error",
                "rt_abi_version",
                "rt_refit_nodes", "rt_update_vertices", "rt_update_vertices_device", "rt_scene_bounds",
                "rt_last_update_timing", "rt_build_bvh", "rt_build_bvh_device", "rt_last_build_timing",
@@ -165,6 +165,7 @@ def lib() -> C.CDLL:
             "rt_scene_image_pack": (C.c_int, [vp, vp, C.c_uint64, vp]),
             "rt_scene_image_load": (C.c_int, [vp, vp, C.c_uint64, vp]),
             "rt_fetch_counts": (C.c_int, [vp, u32, u32, i32, u32, C.POINTER(C.c_uint64)]),
+            "rt_loop_variant_counts": (C.c_int, [vp, u32, u32, i32, u32, C.POINTER(C.c_uint64)]),
             "rt_gather_peak": (C.c_int, [vp, u32, u32, C.POINTER(f32), C.POINTER(C.c_uint64)]),
             "rt_chase_peak": (C.c_int, [vp, u32, u32, u32, C.POINTER(f32), C.POINTER(C.c_uint64)]),
             "rt_chase_latency": (C.c_int, [vp, u32, u32, u32, u32, C.POINTER(f32), C.POINTER(C.c_uint64)]),
@@ -687,6 +688,14 @@ class Renderer:
         return {"inner": int(out[0]), "tri": int(out[1]), "quad_inner": int(out[2]), "quad_tri": int(out[3]),
                 "distinct_inner": int(out[4]), "distinct_tri": int(out[5]), "wave_instructions": int(out[6]),
                 "mixed_instructions": int(out[7])}
+
+    def loop_variant_counts(self, w: int, h: int, depth: int = 1, flags: int = 0):
+        """rt_loop_variant_counts: which copy of the fast traversal's loop one frame's wave traversals
+        took (counting instantiation; RT_FLAG_EXACT_DIV allowed) -> {"closest": [generic, octant 0..7],
+        "any": the same for the shadow traversals}; octant k: bit 0 / 1 / 2 set = x / y / z negative."""
+        out = (C.c_uint64 * 18)()
+        _check(lib().rt_loop_variant_counts(self._h, w, h, depth, flags, out), self._h)
+        return {"closest": [int(v) for v in out[0:9]], "any": [int(v) for v in out[9:18]]}
 
     def chase_peak(self, table_records: int = 16384, iters: int = 512, group: int = 4):
         """rt_chase_peak: (ms per launch, waves) of the dependent-iteration latency roof."""

@@ -8,7 +8,11 @@ The loop is the one whose header precedes the kernel's first `buffer_load_dwordx
 reads through the scalar cache).  Blocks are listed in program order with their instruction
 counts; a trip runs the head, then the inner-step and/or the triangle-step blocks (exec-masked:
 a mixed trip runs both), then the tail.
-Usage: python3 scripts/isa_loop.py ASM KERNEL_SYMBOL_PREFIX OUT_PREFIX"""
+A kernel with the octant loops (rt_kernel_body.inc traverse_fast) has several main loops per
+traversal: WHICH (default 0) picks the WHICH-th of them in program order, and the census says how
+many two-input v_min / v_max the loop holds (12 of them: a generic loop; none: an octant loop, or
+the division form, which uses the compiler's own min / max).
+Usage: python3 scripts/isa_loop.py ASM KERNEL_SYMBOL_PREFIX OUT_PREFIX [WHICH]"""
 import re
 import sys
 
@@ -35,13 +39,18 @@ def classify(op):
 
 def main():
     asm, sym, out = sys.argv[1], sys.argv[2], sys.argv[3]
+    which = int(sys.argv[4]) if len(sys.argv) > 4 else 0
     lines = open(asm).read().splitlines()
     start = next(i for i, l in enumerate(lines) if l.startswith(sym) and l.rstrip().endswith(":") or
                  (l.startswith(sym) and ": ;" in l))
     end = next(i for i in range(start + 1, len(lines)) if lines[i].startswith(".Lfunc_end"))
     body = lines[start:end]
-    ld = next(i for i, l in enumerate(body) if "buffer_load_dwordx4" in l and "offset:32" in l)
-    hdr = max(i for i in range(ld) if "Loop Header" in body[i])
+    hdrs = []   # the main loops' headers, in program order
+    for ld in (i for i, l in enumerate(body) if "buffer_load_dwordx4" in l and "offset:32" in l):
+        h = max(i for i in range(ld) if "Loop Header" in body[i])
+        if h not in hdrs:
+            hdrs.append(h)
+    hdr = hdrs[which]
     label = body[hdr].split(":")[0]
     # the loop's blocks: the header and every block the assembler marks "in Loop: Header=<it>" (Depth=1)
     tag = "Header=" + label[2:]   # ".LBB51_7" -> "Header=BB51_7"
@@ -54,6 +63,7 @@ def main():
             loop.append(l)
     blocks, cur = [], {"name": "(entry)", "n": 0, "cls": {}}
     waits = []
+    minmax = {}
     for l in loop:
         s = l.strip()
         if re.match(r"^(\.LBB\w+|; %bb\.\d+):", s):
@@ -64,6 +74,8 @@ def main():
             continue
         op = s.split()[0]
         c = classify(op)
+        if re.match(r"v_(min|max)3?_f32", op):
+            minmax[op] = minmax.get(op, 0) + 1
         cur["n"] += 1
         cur["cls"][c] = cur["cls"].get(c, 0) + 1
         if c == "waitcnt":
@@ -76,7 +88,9 @@ def main():
     with open(out + ".s", "w") as f:
         f.write("\n".join(loop) + "\n")
     with open(out + ".txt", "w") as f:
-        f.write(f"kernel {sym}, loop {label}: {sum(b['n'] for b in blocks)} instructions in {len(blocks)} blocks\n")
+        f.write(f"kernel {sym}, main loop {which} of {len(hdrs)}, {label}: {sum(b['n'] for b in blocks)} instructions "
+                f"in {len(blocks)} blocks\n")
+        f.write("min/max: " + (", ".join(f"{k} {v}" for k, v in sorted(minmax.items())) or "none") + "\n")
         f.write("by class: " + ", ".join(f"{k} {v}" for k, v in sorted(tot.items())) + "\n\nblocks in program order:\n")
         for b in blocks:
             f.write(f"  {b['name']:12s} {b['n']:4d}  " + ", ".join(f"{k} {v}" for k, v in sorted(b["cls"].items())) + "\n")

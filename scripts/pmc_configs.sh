@@ -8,9 +8,12 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$ROOT}" || exit 1
 export GPU_MAX_HW_QUEUES=16
 out=$1; cfgs=$2; shift 2
-# PMC_SETS=occ: only the two occupancy passes
+# PMC_SETS=occ: only the two occupancy passes; PMC_SETS=issue: only the two instruction-issue passes
 if [ "${PMC_SETS:-all}" = occ ]; then
   sets=("MeanOccupancyPerCU" "MeanOccupancyPerActiveCU")
+elif [ "${PMC_SETS:-all}" = issue ]; then
+  sets=("GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES"
+        "SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_INSTS_SMEM")
 else
   sets=("MeanOccupancyPerCU" "MeanOccupancyPerActiveCU" "FETCH_SIZE" "WRITE_SIZE"
         "GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVES"
