@@ -90,10 +90,12 @@ enum {
                                 waves; pixels are identical either way */
     RT_FLAG_EXACT_DIV = 4u,  /* force the division form of the slab test (volumeRender.cl:614-615) instead
                                 of the bit-identical fast quotient; for A/B only */
-    RT_FLAG_STATIC_ORDER = 16u /* keep the static XCD-dealt block order instead of the adaptive
+    RT_FLAG_STATIC_ORDER = 16u, /* keep the static XCD-dealt block order instead of the adaptive
                                 longest-first order built from the per-block times of the context's
                                 latest rebuild launch on the stream slot (every 8th launch;
                                 RTAMD_LPT_EVERY); pixels are identical either way */
+    RT_FLAG_ANY_HIT = 128u   /* rt_trace_rays only: the first triangle the traversal accepts (what the
+                                shadow ray does, volumeRender.cl:986) instead of the closest one */
 };
 
 #define RT_MAX_DEPTH 8       /* reference: RAY_TRACE_DEPTH 3 (volumeRender.cl:12) */
@@ -523,9 +525,50 @@ int rt_chase_latency(rt_ctx* ctx, uint32_t table_records, uint32_t iters, uint32
 int rt_wave_timeline(rt_ctx* ctx, uint32_t w, uint32_t h, int32_t depth, uint32_t flags, int32_t frames, uint32_t* words,
                      uint64_t cap_words, uint64_t* used_words);
 
-/* Traversals of the last frame that outgrew the fast kernel's LDS stack and
- * restarted in-kernel with the general traversal (same result, slower ray);
- * diagnostics, synchronizes the stream. */
+/* Ray queries: closest hit or any hit for rays the caller supplies, against the
+ * context's scene (uploaded, built, refit or loaded), in the arithmetic the flags select.
+ *
+ * A ray is ray_init(o, d) exactly as the render path builds its rays (volumeRender.cl:205-212): d
+ * need not be unit length and is normalised by the same normalize, inv_dir is computed the same way,
+ * and every t is a distance along the normalised direction.  The traversal is the reference's
+ * (volumeRender.cl:776-1009) with tHit initialised to the ray's tmax instead of the constant
+ * RT_RAY_TMAX_DEFAULT.  A triangle is accepted iff 0.001f < t < tHit; 0.001f is the reference's TMIN
+ * and is a constant here, NOT a per-ray value.
+ *   closest hit (default): id = 3 * triangle index of the closest accepted triangle, t its distance;
+ *   any hit (RT_FLAG_ANY_HIT): the first triangle the traversal accepts, with its t;
+ *   a miss: id = -1 and t = the ray's tmax word, bit for bit.
+ * No rt_params are read (no scene-box early-out; rt_set_params is not needed).
+ * Invalid rays -- a non-finite origin or direction component, a zero direction, a NaN tmax -- and rays
+ * with tmax <= 0.001f (which can accept nothing) are reported as a miss without being traversed; the
+ * other rays of the buffer are unaffected.  +inf is a legal tmax.  `reserved` is ignored.
+ * A traversal that overflows the 65-entry stack is the reference's silent miss, counted by
+ * rt_overflow_count; traversals restarted with the general code are counted by rt_last_deferred.
+ *
+ * flags: RT_FLAG_HW_MATH or RT_FLAG_STRICT_MATH (not both), RT_FLAG_EXACT_DIV, RT_FLAG_ANY_HIT; any
+ * other bit is RT_ERR_INVALID_ARG.  Refused before any GPU work: RT_ERR_INVALID_ARG for a NULL ctx, a
+ * NULL pointer with n > 0, n < 0 or n > 2^30, a bad flag, a misaligned device pointer;
+ * RT_ERR_NO_SCENE without a scene.  n == 0 is RT_OK and launches nothing.
+ *
+ * rt_trace_rays is synchronous: it copies the rays up and the hits back (pinned, device-mapped
+ * caller memory is used directly, as by rt_render).  rt_trace_rays_device takes device pointers
+ * (d_rays 16-byte aligned, d_hits 8-byte aligned) whose contents are produced on `stream` (NULL =
+ * the context's stream) and returns after enqueue, like rt_render_device; a scene replacement or
+ * vertex update called after it waits for the query, exactly as for frames.
+ * rt_last_query_timing: the HIP-event time of the last query's kernel (ms); synchronizes on it. */
+typedef struct rt_ray { float ox, oy, oz, tmax; float dx, dy, dz; uint32_t reserved; } rt_ray;  /* 32 B */
+typedef struct rt_hit { int32_t id; float t; } rt_hit;                                          /*  8 B */
+#define RT_RAY_TMAX_DEFAULT 4294967296.0f   /* HitRecordInit: t = UINT_MAX as float */
+#ifdef __cplusplus
+static_assert(sizeof(rt_ray) == 32, "rt_ray is 32 bytes");
+static_assert(sizeof(rt_hit) == 8, "rt_hit is 8 bytes");
+#endif
+int rt_trace_rays(rt_ctx* ctx, const rt_ray* rays, int64_t n, uint32_t flags, rt_hit* hits);
+int rt_trace_rays_device(rt_ctx* ctx, const rt_ray* d_rays, int64_t n, uint32_t flags, rt_hit* d_hits, void* stream);
+int rt_last_query_timing(rt_ctx* ctx, float* ms);
+
+/* Traversals of the last frame (or of the last ray query, if that came later) that outgrew the
+ * fast kernel's LDS stack and restarted in-kernel with the general traversal (same result,
+ * slower ray); diagnostics, synchronizes the stream. */
 int rt_last_deferred(rt_ctx* ctx, uint32_t* count);
 
 /* Device stack-overflow counter (reference: silent miss, volumeRender.cl:914). */

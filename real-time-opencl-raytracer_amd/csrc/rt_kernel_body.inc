@@ -546,15 +546,17 @@ __device__ __forceinline__ bool traverse_fast(const DevScene& S, Ray& ray, float
 }
 
 // Closest-hit / any-hit of one ray: the fast traversal, restarted with the general
-// code when its stack outgrows the LDS part (counted in O.restarts).
+// code when its stack outgrows the LDS part (counted in O.restarts).  t_restart: what t was on
+// entry, which the restart begins from again (a frame's rays: HitRecordInit's constant; a query's
+// ray: its own tmax).
 template <bool CLOSEST, bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true, bool OCTS = false>
 __device__ __forceinline__ int trace(const DevScene& S, const Outputs& O, Ray& ray, float& t, const Stack& st,
-                                     bool& overflow) {
+                                     bool& overflow, float t_restart = 4294967296.0f) {
     int hit;
     if (FASTONLY) {
         if (traverse_fast<CLOSEST, TR, SEL, GUARD, OCTS>(S, ray, t, st, hit)) return hit;
         atomicAdd(O.restarts, 1u);
-        t = 4294967296.0f;
+        t = t_restart;
     }
     return traverse<CLOSEST>(S, ray, t, st, overflow);
 }
@@ -987,6 +989,63 @@ __global__ void __launch_bounds__(256, TR == 1 ? 4 : (kMath == 2 ? RTK_WFB_REF_W
     if (TR == 2) {
         const uint32_t t_end = (uint32_t)__builtin_amdgcn_s_memrealtime();
         rtk::timeline_store(O, blockIdx.x * 4u + (uint32_t)wave, t_start, t_end, &s_fc[wave * rtk::kTlWords], ngroups);
+    }
+}
+
+// ============================================================================
+// Ray queries (rt_trace_rays, DESIGN.md 18): closest hit (ANY = false) or any hit of rays read
+// from memory.  A persistent grid, as the bounce kernel's: a wave takes 64 rays at a time (group g
+// = rays [64 g, 64 g + 64), rtk::grab_group), a lane reads its ray as two 16-B loads, traces it
+// with the frame kernels' trace<> from its own tmax, and stores its rt_hit as one 8-B store (a
+// wave's 512 B are contiguous).  No Frame, no shading, no queues.
+// A lane whose ray is invalid (a non-finite origin or direction component, a zero direction, a NaN
+// tmax) or can accept nothing (tmax <= kTmin) sits the traversal out, as a bounce kernel's lane
+// past the end of its queue does, and reports a miss; a miss's t is the ray's tmax word itself.
+// The global part of the stack is one column per lane of the GRID (not per ray), so its size does
+// not depend on n.
+// In S_ref both instantiations of the fast kernel run the octant loops (OCTS): without shading
+// they stay within 8 waves' registers with no scratch (DESIGN.md 18).  Record offsets come from a
+// select (SEL), as in the depth-1 frame kernel: incoherent rays 0.950 vs 0.999 ms for C3's 2.07 M,
+// the frame's own rays the same within the spread.
+// ============================================================================
+__device__ __forceinline__ bool query_ray_ok(const float4& a, const float4& b) {
+    const bool fin = fabsf(a.x) < __builtin_inff() && fabsf(a.y) < __builtin_inff() && fabsf(a.z) < __builtin_inff() &&
+                     fabsf(b.x) < __builtin_inff() && fabsf(b.y) < __builtin_inff() && fabsf(b.z) < __builtin_inff();
+    const bool zero = b.x == 0.0f && b.y == 0.0f && b.z == 0.0f;
+    return fin && !zero && a.w > kTmin;   // (false for a NaN tmax too)
+}
+
+template <bool ANY, bool FASTONLY>
+__global__ void __launch_bounds__(256, kMath == 2 ? RTK_QUERY_REF_WAVES : RTK_QUERY_WAVES) query_kernel(DevScene S, Outputs O, rtk::Query Q) {
+    __shared__ uint32_t s_stack[4][rtk::kLdsRows][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t ngroups = (Q.n + rtk::kSegRays - 1) / rtk::kSegRays;
+    uint32_t home = blockIdx.x & (rtk::kCursors - 1u);
+    Stack st;
+    st.lds = &s_stack[wave][rtk::kLdsGuard][lane];
+    st.glb = O.gstack + ((size_t)blockIdx.x * rtk::kBlockThreads + threadIdx.x);
+    st.gstride = O.local_pixels;   // the lanes launched
+    for (;;) {
+        const uint32_t g = rtk::grab_group(Q.fetch, ngroups, home);
+        if (g == rtk::kNoGroup) break;
+        const uint32_t i = g * rtk::kSegRays + (uint32_t)lane;
+        const bool inside = i < Q.n;   // (false only in the last group's tail)
+        float4 a = make_float4(0, 0, 0, 0), b = a;
+        if (inside) {
+            const float4* rp = Q.rays + (size_t)i * 2;
+            a = rp[0];
+            b = rp[1];
+        }
+        const uint32_t tmax_word = __float_as_uint(a.w);
+        int hit = -1;
+        float t = a.w;
+        bool overflow = false;
+        if (inside && query_ray_ok(a, b)) {
+            Ray ray = ray_init(F3{a.x, a.y, a.z}, F3{b.x, b.y, b.z});
+            hit = trace<!ANY, FASTONLY, 0, true, true, kOctLoops>(S, O, ray, t, st, overflow, a.w);
+        }
+        if (inside) Q.hits[i] = make_uint2((uint32_t)hit, hit >= 0 ? __float_as_uint(t) : tmax_word);
+        if (overflow) atomicAdd(O.overflow, 1ull);
     }
 }
 

@@ -73,6 +73,17 @@
                             // 0.755 / 0.760 / 0.757 ms, one frame per launch 0.827 vs 0.836 at 75 %, one frame alone
                             // 1.28 vs 1.25: profiles/r06/ab/c5_grid_pct_ab*.txt; round 4 at one frame per launch: 75 %)
 #endif
+#ifndef RTK_QUERY_REF_WAVES
+#define RTK_QUERY_REF_WAVES 8   // waves per SIMD the S_ref query kernels are bounded to (no scratch at 8: DESIGN.md 18)
+#endif
+#ifndef RTK_QUERY_WAVES
+#define RTK_QUERY_WAVES 7       // the same for S_strict / S_hw, as their other kernels
+#endif
+#ifndef RTK_QUERY_GRID_PCT
+#define RTK_QUERY_GRID_PCT 75   // persistent query grid, percent of the blocks the chip holds at once (C3's 2.07 M primary
+                                // rays, closest hit / incoherent rays: 50 % 0.248 / 0.955 ms, 75 % 0.232 / 0.998, 100 % 0.242 /
+                                // 1.040: DESIGN.md 18)
+#endif
 #ifndef RTK_FB_WAVES
 #define RTK_FB_WAVES 8      // waves per SIMD the S_ref depth-1 kernel is bounded to
 #endif
@@ -204,6 +215,15 @@ __device__ __forceinline__ uint32_t grab_group(uint32_t* cursors, uint32_t ngrou
     home = __builtin_amdgcn_readfirstlane(h);
     return __builtin_amdgcn_readfirstlane(g);
 }
+
+// A ray query's launch (rt_trace_rays, query_kernel): rays are rt_ray as two float4 {o.xyz, tmax},
+// {d.xyz, reserved}, hits rt_hit as one uint2 {id, t}; n <= 2^30, so ray and group indices fit 32 bits.
+struct Query {
+    const float4* rays;
+    uint2* hits;
+    uint32_t n;
+    uint32_t* fetch;    // the launch's work cursors (grab_group), zeroed before it
+};
 
 struct Outputs {
     uint32_t* out;
@@ -1042,6 +1062,9 @@ struct rt_ctx {
         uint32_t* d_lpt = nullptr; size_t lpt_cap = 0;     //   the longest-first order built from them,
         uint32_t* d_done = nullptr;                        //   and the finished-block counter
         uint64_t cost_key = 0; bool cost_ready = false;
+        // a query slot (kQueryKey): the launch's work cursors and restart count, and the events around its kernel
+        uint32_t* d_qcnt = nullptr;
+        hipEvent_t qev[2] = {nullptr, nullptr};
     };
     static constexpr int kMaxSlots = 16;
     std::vector<FrameSlot> slots;
@@ -1055,6 +1078,13 @@ struct rt_ctx {
     std::vector<OrderTab> orders;
     uint32_t scene_gen = 0;                                   // bumped by every upload
     int wf_grid[3] = {0, 0, 0};   // persistent wavefront grid per math mode
+    // ray queries: the persistent grid per math mode, the host form's staging, and the
+    // slot of the last query while no frame has come after it (rt_last_deferred, rt_last_query_timing)
+    int query_grid[3] = {0, 0, 0};
+    float4* d_qrays = nullptr; size_t qrays_cap = 0;
+    uint2* d_qhits = nullptr; size_t qhits_cap = 0;
+    FrameSlot* query_slot = nullptr;
+    bool query_last = false;
     struct { bool on = false; unsigned long long* d_counts = nullptr; } trace;   // rt_fetch_counts
     struct {                                                                    // rt_wave_timeline
         bool on = false;
@@ -1166,9 +1196,11 @@ static int ensure(rt_ctx* c, T*& p, size_t& cap, size_t n) {
 
 static void free_slot(rt_ctx::FrameSlot& f) {
     for (void* p : {(void*)f.d_gstack, (void*)f.d_wq[0], (void*)f.d_wq[1], (void*)f.d_wcnt,
-                    (void*)f.d_perm, (void*)f.d_seg, (void*)f.d_cost, (void*)f.d_lpt, (void*)f.d_done})
+                    (void*)f.d_perm, (void*)f.d_seg, (void*)f.d_cost, (void*)f.d_lpt, (void*)f.d_done, (void*)f.d_qcnt})
         if (p) (void)hipFree(p);
     if (f.idle) (void)hipEventDestroy(f.idle);
+    for (hipEvent_t e : f.qev)
+        if (e) (void)hipEventDestroy(e);
     f = rt_ctx::FrameSlot{};
 }
 
@@ -1333,6 +1365,10 @@ template <int M> struct Kernels;
             return next ? (void*)NS::first_bounce_kernel<true, true, 1> : (void*)NS::first_bounce_kernel<true, false, 1>; \
         }                                                                                                  \
         static void* traced_bounce() { return (void*)NS::wf_bounce_kernel<true, 1>; }                     \
+        static void* query(bool any, bool fast) {                                                          \
+            return any ? (fast ? (void*)NS::query_kernel<true, true> : (void*)NS::query_kernel<true, false>) \
+                       : (fast ? (void*)NS::query_kernel<false, true> : (void*)NS::query_kernel<false, false>); \
+        }                                                                                                  \
         static void* batch(bool fast, bool next) {                                                         \
             return fast ? (next ? (void*)NS::first_bounce_batch_kernel<true, true> : (void*)NS::first_bounce_batch_kernel<true, false>) \
                         : (next ? (void*)NS::first_bounce_batch_kernel<false, true> : (void*)NS::first_bounce_batch_kernel<false, false>); \
@@ -1360,6 +1396,9 @@ static void* kernel_traced_bounce(int m) {
 }
 static void* kernel_bounce(int m, bool fast) {
     return m == 0 ? Kernels<0>::bounce(fast) : m == 1 ? Kernels<1>::bounce(fast) : Kernels<2>::bounce(fast);
+}
+static void* kernel_query(int m, bool any, bool fast) {
+    return m == 0 ? Kernels<0>::query(any, fast) : m == 1 ? Kernels<1>::query(any, fast) : Kernels<2>::query(any, fast);
 }
 // the timeline instantiation (rt_wave_timeline): S_ref, the fast kernels
 static void* kernel_timeline_first(bool next) {
@@ -1573,6 +1612,8 @@ int rt_destroy(rt_ctx* c) {
     if (c->d_t) (void)hipFree(c->d_t);
     if (c->d_rgb) (void)hipFree(c->d_rgb);
     if (c->d_overflow) (void)hipFree(c->d_overflow);
+    if (c->d_qrays) (void)hipFree(c->d_qrays);
+    if (c->d_qhits) (void)hipFree(c->d_qhits);
     for (auto& f : c->slots) free_slot(f);
     for (auto& o : c->orders) (void)hipFree(o.d);
     if (c->tline.d_words) (void)hipFree(c->tline.d_words);
@@ -2207,6 +2248,7 @@ static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint3
     rt_ctx::FrameSlot& L = *Lp;
     c->last_slot = &L;
     c->last_group.clear();
+    c->query_last = false;
     const int math = (flags & RT_FLAG_STRICT_MATH) ? 0 : (flags & RT_FLAG_HW_MATH) ? 1 : 2;
 
     rtk::Frame F;
@@ -2682,10 +2724,144 @@ int rt_timing_average(rt_ctx* c, int32_t n, float* total_ms, float* traverse_ms)
     return RT_OK;
 }
 
+// ---- ray queries ----
+// A query takes a frame slot of its own kind per stream (kQueryKey: no tiling has that key), so
+// install_scene and update_vertices wait for it through the slot's idle event as they do for frames,
+// and queries on different streams may run concurrently.  The slot holds the spill stack (one
+// column per lane of the persistent grid, sized once: the grid is the context's), the launch's
+// work cursors and restart count (zeroed on the stream before every launch) and the two events
+// around the kernel.
+constexpr uint64_t kQueryKey = 1ull << 62;
+constexpr int64_t kMaxQueryRays = 1ll << 30;
+constexpr uint32_t kQueryFlags = RT_FLAG_HW_MATH | RT_FLAG_STRICT_MATH | RT_FLAG_EXACT_DIV | RT_FLAG_ANY_HIT;
+
+// the refusals that need no GPU; `who` names the entry point in the message
+static int query_check(rt_ctx* c, const char* who, const void* rays, int64_t n, uint32_t flags, const void* hits) {
+    if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
+    if (n < 0 || n > kMaxQueryRays) return set_err(c, std::string(who) + ": n must be 0..2^30", RT_ERR_INVALID_ARG);
+    if (n > 0 && (!rays || !hits)) return set_err(c, std::string(who) + ": rays or hits is NULL", RT_ERR_INVALID_ARG);
+    if (flags & ~kQueryFlags) return set_err(c, std::string(who) + ": a flag that is not a ray query's", RT_ERR_INVALID_ARG);
+    if ((flags & RT_FLAG_STRICT_MATH) && (flags & RT_FLAG_HW_MATH))
+        return set_err(c, std::string(who) + ": RT_FLAG_STRICT_MATH and RT_FLAG_HW_MATH exclude each other", RT_ERR_INVALID_ARG);
+    if (!c->have_scene) return set_err(c, std::string(who) + ": no scene uploaded", RT_ERR_NO_SCENE);
+    return RT_OK;
+}
+
+// checked arguments, n > 0
+static int query_enqueue(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32_t flags, rt_hit* d_hits, hipStream_t s) {
+    int rc = RT_OK;
+    rt_ctx::FrameSlot* Lp = nullptr;
+    if ((rc = slot_for(c, (void*)s, kQueryKey, &Lp))) return rc;
+    rt_ctx::FrameSlot& L = *Lp;
+    const int math = (flags & RT_FLAG_STRICT_MATH) ? 0 : (flags & RT_FLAG_HW_MATH) ? 1 : 2;
+    const bool any = (flags & RT_FLAG_ANY_HIT) != 0;
+    const Scene& sc = c->scene;
+    rtk::DevScene S{sc.wnodes(),
+                    sc.tris(),
+                    sc.shade(),
+                    sc.leaf(),
+                    (uint32_t)(sc.n_wnodes4 * 16),
+                    (uint32_t)((sc.n_wnodes4 + sc.n_tris4) * 16),
+                    sc.root,
+                    sc.n_inner,
+                    (sc.fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,
+                    sc.clean};
+    const bool fast = S.clean != 0 && !sc.split;   // as for frames (render_frames)
+    if (!c->query_grid[math]) {
+        int cus = 0, b1 = 0;
+        HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, (const void*)kernel_query(math, false, true), 256, 0));
+        c->query_grid[math] = std::max(8, std::max(b1, 1) * cus * RTK_QUERY_GRID_PCT / 100);
+    }
+    // the stack columns are sized for the mode's whole grid, whatever n is: a later, larger query allocates nothing
+    const size_t full = (size_t)c->query_grid[math];
+    const uint32_t ngroups = (uint32_t)((n + rtk::kSegRays - 1) / rtk::kSegRays);
+    const uint32_t grid = (uint32_t)std::min<size_t>(full, (ngroups + 3u) / 4u);
+    if ((rc = ensure(c, L.d_gstack, L.gstack_cap, full * rtk::kBlockThreads * rtk::kGlobalStack))) return rc;
+    if (!L.d_qcnt) {
+        size_t cap = 0;
+        if ((rc = ensure(c, L.d_qcnt, cap, rtk::kCursorSet + 32))) return rc;
+    }
+    for (hipEvent_t& e : L.qev)
+        if (!e) HIPC(c, hipEventCreate(&e));
+    rtk::Outputs O{};
+    O.gstack = L.d_gstack;
+    O.overflow = c->d_overflow;
+    O.restarts = L.d_qcnt + rtk::kCursorSet;
+    O.local_pixels = (uint64_t)grid * rtk::kBlockThreads;   // the stack's stride: the lanes launched
+    rtk::Query Q{(const float4*)d_rays, (uint2*)d_hits, (uint32_t)n, L.d_qcnt};
+    HIPC(c, hipMemsetAsync(L.d_qcnt, 0, (rtk::kCursorSet + 32) * sizeof(uint32_t), s));
+    (void)hipGetLastError();
+    void* args[] = {&S, &O, &Q};
+    HIPC(c, hipExtLaunchKernel(kernel_query(math, any, fast), dim3(grid), dim3(rtk::kBlockThreads), args, 0, s, L.qev[0],
+                               L.qev[1], 0));
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(L.idle, s));
+    c->query_slot = &L;
+    c->query_last = true;
+    return RT_OK;
+}
+
+int rt_trace_rays_device(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32_t flags, rt_hit* d_hits, void* stream) {
+    if (const int rc = query_check(c, "rt_trace_rays_device", d_rays, n, flags, d_hits)) return rc;
+    if (n == 0) return RT_OK;
+    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_hits & 7u))
+        return set_err(c, "rt_trace_rays_device: d_rays must be 16-byte aligned and d_hits 8-byte aligned", RT_ERR_INVALID_ARG);
+    HIPC(c, hipSetDevice(c->device));
+    return query_enqueue(c, d_rays, n, flags, d_hits, stream ? (hipStream_t)stream : c->stream);
+}
+
+int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int64_t n, uint32_t flags, rt_hit* hits) {
+    if (const int rc = query_check(c, "rt_trace_rays", rays, n, flags, hits)) return rc;
+    if (n == 0) return RT_OK;
+    HIPC(c, hipSetDevice(c->device));
+    // pinned host memory the device can reach (hipHostMalloc, or registered as mapped) is used
+    // directly, as by rt_render; anything else goes through the context's staging
+    auto mapped = [](const void* p, size_t align) -> void* {
+        hipPointerAttribute_t pa;
+        if (hipPointerGetAttributes(&pa, p) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer &&
+            !((uintptr_t)pa.devicePointer & (align - 1)))
+            return pa.devicePointer;
+        (void)hipGetLastError();   // pageable memory: not an error
+        return nullptr;
+    };
+    const rt_ray* d_rays = (const rt_ray*)mapped(rays, 16);
+    rt_hit* d_hits = (rt_hit*)mapped(hits, 8);
+    int rc = RT_OK;
+    if (!d_rays) {
+        if ((rc = ensure(c, c->d_qrays, c->qrays_cap, (size_t)n * 2))) return rc;
+        HIPC(c, hipMemcpyAsync(c->d_qrays, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+        d_rays = (const rt_ray*)c->d_qrays;
+    }
+    const bool back = !d_hits;
+    if (back) {
+        if ((rc = ensure(c, c->d_qhits, c->qhits_cap, (size_t)n))) return rc;
+        d_hits = (rt_hit*)c->d_qhits;
+    }
+    if ((rc = query_enqueue(c, d_rays, n, flags, d_hits, c->stream))) return rc;
+    if (back) HIPC(c, hipMemcpyAsync(hits, d_hits, (size_t)n * sizeof(rt_hit), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, wait_ctx(c, c->stream));
+    return RT_OK;
+}
+
+int rt_last_query_timing(rt_ctx* c, float* ms) {
+    if (!c || !ms) return set_err(c, "rt_last_query_timing: invalid argument", RT_ERR_INVALID_ARG);
+    if (!c->query_slot || !c->query_slot->qev[1]) return set_err(c, "rt_last_query_timing: no ray query yet", RT_ERR_NO_SCENE);
+    HIPC(c, hipEventSynchronize(c->query_slot->qev[1]));
+    HIPC(c, hipEventElapsedTime(ms, c->query_slot->qev[0], c->query_slot->qev[1]));
+    return RT_OK;
+}
+
 int rt_last_deferred(rt_ctx* c, uint32_t* count) {
     if (!c || !count) return RT_ERR_INVALID_ARG;
     *count = 0;
     // the last frame: one slot, or every row group of the last grouped rt_render
+    if (c->query_last && c->query_slot) {   // a ray query came after the last frame: its restarts
+        rt_ctx::FrameSlot* L = c->query_slot;
+        HIPC(c, hipEventSynchronize(L->idle));
+        HIPC(c, hipMemcpy(count, L->d_qcnt + rtk::kCursorSet, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return RT_OK;
+    }
     std::vector<rt_ctx::FrameSlot*> ls = c->last_group;
     if (ls.empty()) ls.push_back(c->last_slot);
     for (rt_ctx::FrameSlot* L : ls) {

@@ -35,6 +35,8 @@ RT_FLAG_STATIC_ORDER = 16
 RT_FLAG_WAVEFRONT = 8
 RT_FLAG_WF_SORT = 32
 RT_FLAG_STRICT_MATH = 64
+RT_FLAG_ANY_HIT = 128          # trace_rays only: the first accepted triangle instead of the closest
+RT_RAY_TMAX_DEFAULT = 4294967296.0   # HitRecordInit: t = UINT_MAX as float
 RT_MAX_DEPTH = 8
 RT_BUILD_EXTENT_KEYS = 0x100   # ORed into a builder's max_leaf: extent-aware Morton keys
 RT_MAX_BATCH = int(os.environ.get("RTAMD_MAX_BATCH", "8"))   # rt_render_device_batch frames per launch (RTAMD_MAX_BATCH: an A/B build's)
@@ -63,6 +65,20 @@ class rt_aux(C.Structure):
 
 class rt_tiling(C.Structure):
     _fields_ = [("rank", C.c_int32), ("nranks", C.c_int32), ("band_rows", C.c_int32), ("reserved", C.c_int32)]
+
+
+class rt_ray(C.Structure):
+    _fields_ = [("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float), ("tmax", C.c_float),
+                ("dx", C.c_float), ("dy", C.c_float), ("dz", C.c_float), ("reserved", C.c_uint32)]
+
+
+class rt_hit(C.Structure):
+    _fields_ = [("id", C.c_int32), ("t", C.c_float)]
+
+
+# the same two records as numpy dtypes (trace_rays' buffers)
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("reserved", np.uint32)])
+HIT_DTYPE = np.dtype([("id", np.int32), ("t", np.float32)])
 
 
 class rt_mesh_view(C.Structure):
@@ -97,7 +113,7 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_refit_nodes", "rt_update_vertices", "rt_update_vertices_device", "rt_scene_bounds",
                "rt_last_update_timing", "rt_build_bvh", "rt_build_bvh_device", "rt_last_build_timing",
                "rt_build_scene", "rt_build_scene_device", "rt_last_scene_build_timing", "rt_refit_level_counts",
-               "rt_scene_sah"]
+               "rt_scene_sah", "rt_trace_rays", "rt_trace_rays_device", "rt_last_query_timing"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
                 "rt_mesh_load_dae", "rt_mesh_save_dae",
                 "rt_mesh_gen_cornell", "rt_mesh_gen_torus_knot", "rt_mesh_gen_heightfield", "rt_mesh_gen_random",
@@ -190,6 +206,9 @@ def lib() -> C.CDLL:
             "rt_last_scene_build_timing": (C.c_int, [vp, C.POINTER(f32)]),
             "rt_refit_level_counts": (C.c_int, [vp, C.POINTER(u32), i32, C.POINTER(i32)]),
             "rt_scene_sah": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+            "rt_trace_rays": (C.c_int, [vp, vp, C.c_int64, u32, vp]),
+            "rt_trace_rays_device": (C.c_int, [vp, vp, C.c_int64, u32, vp, vp]),
+            "rt_last_query_timing": (C.c_int, [vp, C.POINTER(f32)]),
             "rt_bvh_build_lbvh": (C.c_int, [vp, i32, C.POINTER(vp)]),
             "rt_mesh_create": (vp, []),
             "rt_mesh_destroy": (None, [vp]),
@@ -242,6 +261,28 @@ def _check(code: int, ctx=None):
     if code != 0:
         msg = lib().rt_last_error(ctx)
         raise RtError(code, msg.decode() if msg else "")
+
+
+def pack_rays(origins, directions, tmax=None) -> np.ndarray:
+    """n rt_ray records (RAY_DTYPE) from float32 (n, 3) origins and directions and tmax (None =
+    RT_RAY_TMAX_DEFAULT, a scalar, or float32[n], whose bits are kept: a NaN's payload too)."""
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("pack_rays: origins and directions differ in shape")
+    rays = np.zeros(o.shape[0], RAY_DTYPE)
+    rays["o"] = o
+    rays["d"] = d
+    if tmax is None:
+        rays["tmax"] = np.float32(RT_RAY_TMAX_DEFAULT)
+    elif np.ndim(tmax) == 0:
+        rays["tmax"] = np.float32(tmax)
+    else:
+        t = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+        if t.shape[0] != o.shape[0]:
+            raise ValueError("pack_rays: tmax has another length than the rays")
+        rays["tmax"].view(np.uint32)[...] = t.view(np.uint32)
+    return rays
 
 
 def params_to_array(p: rt_params) -> np.ndarray:
@@ -843,6 +884,34 @@ class Renderer:
                 _check(rc, hdl)
         return launch
 
+    def trace_rays(self, origins, directions, tmax=None, any_hit: bool = False, flags: int = 0):
+        """rt_trace_rays: closest hit (or, any_hit, the first accepted triangle) of n caller-supplied
+        rays against the context's scene -> (ids int32[n], t float32[n]).  `origins`, `directions`:
+        float32 (n, 3); a direction need not be unit length, t is a distance along the normalised one.
+        `tmax`: None (RT_RAY_TMAX_DEFAULT), a scalar or float32[n]; its bits reach the kernel as given.
+        A miss is id -1 with t = the ray's tmax, bit for bit.  flags: a math flag, RT_FLAG_EXACT_DIV."""
+        rays = pack_rays(origins, directions, tmax)
+        hits = np.zeros(rays.shape[0], HIT_DTYPE)
+        _check(lib().rt_trace_rays(self._h, _ptr(rays), rays.shape[0], flags | (RT_FLAG_ANY_HIT if any_hit else 0),
+                                   _ptr(hits)), self._h)
+        return hits["id"].copy(), hits["t"].copy()
+
+    def trace_rays_device(self, d_rays: int, n: int, d_hits: int, any_hit: bool = False, flags: int = 0,
+                          stream: Optional[int] = None) -> None:
+        """rt_trace_rays_device: n rt_ray at device address d_rays (16-byte aligned) -> n rt_hit at
+        d_hits (8-byte aligned), enqueued on `stream` (None = the ctx's own), where the rays are
+        produced; returns after enqueue."""
+        _stream_arg(stream)
+        _check(lib().rt_trace_rays_device(self._h, C.c_void_p(d_rays or None), n,
+                                          flags | (RT_FLAG_ANY_HIT if any_hit else 0), C.c_void_p(d_hits or None),
+                                          C.c_void_p(stream or None)), self._h)
+
+    def last_query_ms(self) -> float:
+        """rt_last_query_timing: kernel time of the last trace_rays / trace_rays_device (ms)."""
+        ms = C.c_float()
+        _check(lib().rt_last_query_timing(self._h, C.byref(ms)), self._h)
+        return ms.value
+
     def last_kernel_ms(self) -> float:
         """All kernels of the last frame (ms, HIP events on the launch stream)."""
         t = C.c_float()
@@ -862,7 +931,8 @@ class Renderer:
         return t.value, k.value
 
     def last_deferred(self) -> int:
-        """Traversals of the last frame that restarted with the general code (stack deeper than LDS)."""
+        """Traversals of the last frame (or of the last ray query, if that came later) that restarted
+        with the general code (stack deeper than LDS)."""
         v = C.c_uint32()
         _check(lib().rt_last_deferred(self._h, C.byref(v)), self._h)
         return v.value
