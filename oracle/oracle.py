@@ -48,6 +48,8 @@ def lib():
         L.oracle_render.argtypes = [vp, vp, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, C.c_uint32,
                                     C.c_uint32, C.c_int, C.c_uint32, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp,
                                     vp, C.POINTER(ostats), C.c_int]
+        L.oracle_trace_rays.restype = C.c_int
+        L.oracle_trace_rays.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int64, C.c_int, vp, vp, vp]
         L.oracle_normalize.argtypes = [vp, vp]
         L.oracle_ray_tri.restype = C.c_float
         L.oracle_ray_tri.argtypes = [vp, vp, vp, vp, vp]
@@ -100,6 +102,34 @@ def render(scene, params, w, h, depth=3, flags=0, pixels=None, nthreads=None, au
     if aux:
         res.update(hits=hits[:, :depth], t=tv[:, :depth], rgb=rgb)
     return res
+
+
+QUERY_COUNTERS = ("inner", "leaf", "tris", "max_stack", "stack_overflow", "error_miss")
+
+
+def trace_rays(scene, rays, any_hit=False):
+    """Ray queries with the oracle: oracle_trace_rays of rt_oracle.c.
+
+    scene : as for render (only vertices, indices, nodes and tri_indices are read)
+    rays  : n records of 32 bytes {o.xyz, tmax, d.xyz, reserved} (rtamd.pack_rays' layout), any dtype
+    Returns (ids int32[n], t float32[n], stats): a miss is -1 and the ray's tmax word, bit for bit;
+    stats sums inner / leaf / tris / stack_overflow / error_miss over the rays, max_stack is the largest.
+    """
+    g = (lambda k: scene[k]) if isinstance(scene, dict) else (lambda k: getattr(scene, k))
+    arr = {k: np.ascontiguousarray(g(k)) for k in ("vertices", "indices", "nodes", "tri_indices")}
+    raw = np.ascontiguousarray(rays)
+    assert raw.nbytes % 32 == 0, "rays are 32-byte records"
+    words = raw.view(np.uint8).reshape(-1).view(np.float32)
+    n = words.size // 8
+    ids = np.empty(n, np.int32)
+    t = np.empty(n, np.uint32)
+    counters = np.zeros(6, np.uint64)
+    rc = lib().oracle_trace_rays(_p(arr["vertices"]), _p(arr["indices"]), _p(arr["nodes"]), arr["nodes"].shape[0],
+                                 _p(arr["tri_indices"]), arr["tri_indices"].size, _p(words), n, int(bool(any_hit)),
+                                 _p(ids), _p(t), _p(counters))
+    if rc != 0:
+        raise RuntimeError(f"oracle_trace_rays failed: {rc}")
+    return ids, t.view(np.float32), {k: int(v) for k, v in zip(QUERY_COUNTERS, counters)}
 
 
 def sbvh(vertices, indices):

@@ -47,6 +47,7 @@
 #include <math.h>
 #include <float.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 #include <pthread.h>
 
@@ -199,7 +200,7 @@ static int o_traverse(const oscene* s, const oray* ray, float* tHit, int closest
         if (offset_left >= 0) {
             int offset_right = nd->r;
             c->inner++;
-            if (offset_right < 0) return -1;
+            if (offset_right < 0) return -1;            /* these three exits: o_malformed() below restates them */
             if (offset_left >= s->num_nodes) return -1;
             if (offset_right >= s->num_nodes) return -1;
             float n0, f0, n1, f1;
@@ -475,6 +476,72 @@ int oracle_render(const oparams* params, const of4* verts, const int32_t* idx, c
             stats->stack_overflow += jobs[t].st.stack_overflow;
         }
     }
+    return 0;
+}
+
+/*
+ * Ray queries: n caller-supplied rays, records of 8 words {o.xyz, tmax, d.xyz,
+ * reserved}.  A ray with a non-finite origin or direction component, a zero direction or
+ * !(tmax > O_TMIN) is a miss that is not traversed; every other ray is o_ray_init(o, d), tHit = tmax,
+ * o_traverse.  ids[k] = the triangle id or -1; t_words[k] = the bits of t, or on a miss (a stack
+ * overflow or a malformed node included) the ray's tmax word unchanged, NaN payloads kept.
+ * counters[6] = summed inner visits, leaf visits, triangle tests; the largest stack; stack overflows;
+ * error misses: traversals that left o_traverse through one of its malformed-node exits.
+ * o_traverse does not say which -1 it returned, so where the scene has malformed inner nodes at all
+ * a -1 without overflow is traversed again over a copy in which those nodes are empty leaves: the
+ * two runs take the same steps until the first such node is met, which the copy counts as a leaf
+ * visit and survives, so the copy's leaf count is larger iff the ray met one.
+ */
+/* the condition of o_traverse's three malformed-node exits, restated: change both together */
+static int o_malformed(const onode* nd, int32_t nn) {
+    return nd->l >= 0 && (nd->r < 0 || nd->l >= nn || nd->r >= nn);
+}
+int oracle_trace_rays(const of4* verts, const int32_t* idx, const onode* nodes, int32_t num_nodes,
+                      const int32_t* refs, int32_t num_refs, const float* rays, int64_t n, int any_hit,
+                      int32_t* ids, uint32_t* t_words, uint64_t* counters) {
+    if (!verts || !idx || !nodes || num_nodes < 1 || !refs || n < 0 || (n > 0 && (!rays || !ids || !t_words)))
+        return -1;
+    oscene s = {verts, idx, nodes, num_nodes, refs, num_refs, 0, 0, 0, 0};
+    oscene patched = s;
+    onode* copy = 0;
+    for (int32_t k = 0; k < num_nodes && !copy; ++k)
+        if (o_malformed(&nodes[k], num_nodes)) copy = (onode*)malloc(sizeof(onode) * (size_t)num_nodes);
+    if (copy) {
+        memcpy(copy, nodes, sizeof(onode) * (size_t)num_nodes);
+        for (int32_t k = 0; k < num_nodes; ++k)
+            if (o_malformed(&nodes[k], num_nodes)) { copy[k].l = -1; copy[k].off = 0; copy[k].cnt = 0; }
+        patched.nodes = copy;
+    }
+    uint64_t sum[6] = {0, 0, 0, 0, 0, 0};
+    for (int64_t k = 0; k < n; ++k) {
+        const float* r = rays + 8 * k;
+        memcpy(&t_words[k], &r[3], 4);
+        ids[k] = -1;
+        int ok = r[3] > O_TMIN && !(r[4] == 0.0f && r[5] == 0.0f && r[6] == 0.0f);
+        for (int j = 0; j < 7; ++j)
+            if (j != 3 && !(fabsf(r[j]) < INFINITY)) ok = 0;
+        if (!ok) continue;
+        oray ray;
+        o_ray_init(&ray, v3(r[0], r[1], r[2]), v3(r[4], r[5], r[6]));
+        float tHit = r[3];
+        tcount c;
+        memset(&c, 0, sizeof c);
+        int hit = o_traverse(&s, &ray, &tHit, !any_hit, &c);
+        if (hit >= 0) {
+            ids[k] = hit;
+            memcpy(&t_words[k], &tHit, 4);
+        } else if (copy && !c.overflow) {
+            tcount c2;
+            float t2 = r[3];
+            memset(&c2, 0, sizeof c2);
+            o_traverse(&patched, &ray, &t2, !any_hit, &c2);
+            if (c2.leaf > c.leaf) sum[5]++;
+        }
+        sum[0] += c.inner; sum[1] += c.leaf; sum[2] += c.tris; sum[4] += c.overflow;
+        if (c.max_stack > sum[3]) sum[3] = c.max_stack;
+    }
+    free(copy);
+    if (counters) memcpy(counters, sum, sizeof sum);
     return 0;
 }
 

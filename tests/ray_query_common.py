@@ -126,11 +126,11 @@ def oracle_ray_tri(d, o, dirn, tri_id):
     return np.float32(oracle.lib().oracle_ray_tri(_fp(o), _fp(dirn), _fp(v0), _fp(e1), _fp(e2)))
 
 
-def brute_force_closest(d, o, dirs):
-    """The minimum over ALL triangles of oracle_ray_tri within (TMIN, TMAX_DEFAULT): (id, t); ties
+def brute_force_closest(d, o, dirs, tmax=TMAX_DEFAULT):
+    """The minimum over ALL triangles of oracle_ray_tri within (TMIN, tmax): (id, t); ties
     keep the first triangle in index order, so compare t always and ids only where t is unique."""
     dirn = oracle_normalize(dirs)
-    best, bt = -1, TMAX_DEFAULT
+    best, bt = -1, np.float32(tmax)
     for k in range(d["indices"].size // 3):
         t = oracle_ray_tri(d, o, dirn, 3 * k)
         if TMIN < t < bt:

@@ -8,6 +8,8 @@
 // thread counts.
 //
 //   sanitize_main <tmpdir> [obj file]
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -28,6 +30,9 @@ int oracle_render(const void* params, const void* verts, const int32_t* idx, con
 int sbvh_oracle_build(const float* verts, int32_t nv, const int32_t* idx, int32_t ntri, void** nodes_out,
                       int32_t* num_nodes, int32_t** refs_out, int32_t* num_refs);
 void sbvh_oracle_free(void* p);
+int oracle_trace_rays(const void* verts, const int32_t* idx, const void* nodes, int32_t num_nodes, const int32_t* refs,
+                      int32_t num_refs, const float* rays, int64_t n, int any_hit, int32_t* ids, uint32_t* t_words,
+                      uint64_t* counters);
 }
 
 static int g_fail = 0;
@@ -123,6 +128,33 @@ static void exercise(const char* name, rt_mesh* m, const std::string& dir) {
         CHECK(rc1 == 0 && rc4 == 0, "%s: oracle_render", name);
         CHECK(o1 == o4 && h1 == h4 && !std::memcmp(t1.data(), t4.data(), 4 * t1.size()), "%s: threads differ", name);
         CHECK(st.rays[0] > 0, "%s: no primary rays", name);
+    }
+    // ray queries through the oracle: from the eye at the first vertices, then three invalid rays
+    // (a NaN origin, a zero direction, tmax = 0), closest and any hit
+    {
+        const int nq = std::min(v.num_vertices, 256), n = nq + 3;
+        std::vector<float> rays((size_t)n * 8, 0.0f);
+        for (int k = 0; k < n; ++k) {
+            const rt_float4 to = v.vertices[k % nq];
+            float* r = &rays[(size_t)k * 8];
+            r[0] = p.campos.x; r[1] = p.campos.y; r[2] = p.campos.z; r[3] = 4294967296.0f;
+            r[4] = to.x - p.campos.x; r[5] = to.y - p.campos.y; r[6] = to.z - p.campos.z;
+        }
+        rays[(size_t)nq * 8 + 1] = std::nanf("");
+        rays[(size_t)(nq + 1) * 8 + 4] = rays[(size_t)(nq + 1) * 8 + 5] = rays[(size_t)(nq + 1) * 8 + 6] = 0.0f;
+        rays[(size_t)(nq + 2) * 8 + 3] = 0.0f;
+        for (int any = 0; any < 2; ++any) {
+            std::vector<int32_t> ids(n);
+            std::vector<uint32_t> tw(n);
+            uint64_t counters[6];
+            CHECK(oracle_trace_rays(v.vertices, v.indices, bv.nodes, bv.num_nodes, bv.tri_indices, bv.num_tri_indices,
+                                    rays.data(), n, any, ids.data(), tw.data(), counters) == 0, "%s: oracle_trace_rays", name);
+            int hits = 0;
+            for (int k = 0; k < nq; ++k) hits += ids[k] >= 0;
+            CHECK(hits > 0 && counters[2] > 0 && counters[5] == 0, "%s: queries hit nothing", name);
+            for (int k = nq; k < n; ++k)
+                CHECK(ids[k] == -1 && !std::memcmp(&tw[k], &rays[(size_t)k * 8 + 3], 4), "%s: invalid ray %d", name, k);
+        }
     }
     rt_bvh_destroy(b);
     std::printf("%s: %d tris, %d nodes ok\n", name, ntri, bv.num_nodes);

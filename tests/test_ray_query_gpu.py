@@ -12,6 +12,7 @@ import pytest
 
 import rtamd
 from conftest import load_golden
+from ray_edge_common import deep_comb40   # overflow_comb cut to 40 levels: restarts without overflow, rays that hit
 from ray_query_common import (N_RAYS, TMAX_DEFAULT, TMIN, oracle_closest, oracle_normalize, oracle_ray_tri,
                               quantised_frame, reference, scene_arrays)
 
@@ -50,16 +51,6 @@ def same(got, ids, t, label):
 def hit_tmax(ids, t, scale=1.0):
     """Per-ray tmax: scale * t* where the oracle hits, the default elsewhere."""
     return np.where(ids >= 0, (t * np.float32(scale)).astype(np.float32), TMAX_DEFAULT).astype(np.float32)
-
-
-def deep_comb40():
-    """overflow_comb cut to 40 levels: every level pushes, so a stack reaches 41 entries -- deeper than
-    the LDS part (a restart), within the reference's 65 (no overflow) -- and its rays can hit."""
-    d = dict(load_golden("overflow_comb"))
-    nodes = np.array(d["nodes"][:80], np.float32, copy=True)
-    nodes.view(np.int32)[78, 8] = 79   # the last inner node: both children its own leaf, as the fixture's last
-    d["nodes"], d["tri_indices"] = nodes, d["tri_indices"][:40].copy()
-    return d
 
 
 # ---- 1: closest hit against the oracle, incoherent rays ----

@@ -5,7 +5,8 @@ tests/sanitize_main.cpp drives the scene generators, the OBJ / Collada loaders, 
 binned builders, the BVH cache and the camera (csrc/host/*.cpp, the same sources librtamd.so
 is built from, compiled here with g++) and the oracle (oracle/*.c), with every sanitizer
 report fatal (-fno-sanitize-recover=all).  It also checks the product SBVH against the SBVH
-oracle byte for byte and the oracle's frames across thread counts."""
+oracle byte for byte and the oracle's frames across thread counts, and traces ray queries
+(oracle_trace_rays), invalid rays among them."""
 import os
 import shutil
 import subprocess
