@@ -1,9 +1,13 @@
 // Drives csrc/host/refit.cpp (rt_refit_nodes and its plan) alone under AddressSanitizer +
 // UndefinedBehaviorSanitizer (tests/test_refit.py): well-formed trees, and malformed ones that
-// must be refused with RT_ERR_BAD_SCENE without a write or a read out of bounds.
+// must be refused with RT_ERR_BAD_SCENE without a write or a read out of bounds; and a tree of
+// tests/mesh_edge_common.py's chain52 shape (52 heights, the first of 2,039 nodes), with finite
+// vertices, a NaN coordinate, an all-NaN axis and +-3e38.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "refit.hpp"
@@ -61,6 +65,20 @@ Scene bigleaf() {   // leaves of 40, 3, 0 and 35 triangles
     return s;
 }
 
+// A tree over triangles [first, first + count): `chain` one-sided levels (one triangle to the left),
+// then halves.  span[node] = its range.
+int grow(Scene& s, std::vector<std::pair<int, int>>& span, int first, int count, int chain) {
+    const int me = (int)s.nodes.size();
+    s.nodes.push_back(node(-1, -1, first, count));
+    span.push_back({first, first + count});
+    if (count == 1) return me;
+    const int nl = chain > 0 ? 1 : count / 2;
+    const int l = grow(s, span, first, nl, 0);
+    const int r = grow(s, span, first + nl, count - nl, chain > 0 ? chain - 1 : 0);
+    s.nodes[me] = node(l, r, -1, 0);
+    return me;
+}
+
 int refit(Scene& s) {
     return rt_refit_nodes(s.verts.data(), (int32_t)s.verts.size(), s.idx.data(), (int32_t)s.idx.size(), s.nodes.data(),
                           (int32_t)s.nodes.size(), s.refs.data(), (int32_t)s.refs.size());
@@ -88,10 +106,52 @@ bool box_is(const rt_bvh_node& n, const float mn[3], const float mx[3]) {
            n.max.z == mx[2] && n.min.w == 1.0f && n.max.w == 1.0f;
 }
 
+bool same(float a, float b) { return a == b || (std::isnan(a) && std::isnan(b)); }
+
+// every node's box is fmin / fmax over its range, which ignores a NaN unless all operands are one
+void check_spans(const Scene& s, const std::vector<std::pair<int, int>>& span, const char* what) {
+    float mn[3], mx[3];
+    int bad = 0;
+    for (size_t n = 0; n < s.nodes.size(); ++n) {
+        box_of(s, span[n].first, span[n].second, mn, mx);
+        const rt_bvh_node& nd = s.nodes[n];
+        const float gmn[3] = {nd.min.x, nd.min.y, nd.min.z}, gmx[3] = {nd.max.x, nd.max.y, nd.max.z};
+        for (int a = 0; a < 3; ++a) {
+            const bool all_nan = std::isinf(mn[a]) && mn[a] > 0 && std::isinf(mx[a]) && mx[a] < 0;   // box_of's seeds survived
+            if (all_nan ? !(std::isnan(gmn[a]) && std::isnan(gmx[a])) : !(same(gmn[a], mn[a]) && same(gmx[a], mx[a]))) ++bad;
+        }
+    }
+    EXPECT(bad == 0);
+    rtrefit::Plan plan;
+    std::string err;
+    EXPECT(rtrefit::plan_build(s.nodes.data(), (int32_t)s.nodes.size(), (int32_t)s.refs.size(), nullptr, plan, err) == RT_OK);
+    std::printf("%s: ok, %u heights, %u nodes of height 1\n", what, plan.heights(), plan.level_begin[1] - plan.level_begin[0]);
+}
+
 }  // namespace
 
 int main() {
     float mn[3], mx[3];
+    {   // chain52's shape: 39 one-sided levels into 13 balanced ones; then its vertices at the edges
+        Scene s;
+        std::vector<std::pair<int, int>> span;
+        triangles(s, (1 << 12) + 40);
+        grow(s, span, 0, (1 << 12) + 40, 39);
+        EXPECT(refit(s) == RT_OK);
+        check_spans(s, span, "chain52");
+        Scene a = s;
+        a.verts[22].y = NAN;
+        EXPECT(refit(a) == RT_OK);
+        check_spans(a, span, "nan coordinate");
+        Scene e = s;
+        for (int k = 0; k < 3; ++k) { e.verts[60 + k].y = 3.0e38f; e.verts[63 + k].y = -3.0e38f; }
+        EXPECT(refit(e) == RT_OK);
+        check_spans(e, span, "overflowing c2");
+        Scene c = s;
+        for (rt_float4& v : c.verts) v.y = NAN;
+        EXPECT(refit(c) == RT_OK);
+        check_spans(c, span, "nan axis");
+    }
     {   // the comb: 60 heights, one node each; every inner node i bounds triangles i..60
         Scene s = comb(60);
         EXPECT(refit(s) == RT_OK);
