@@ -65,14 +65,38 @@ __device__ __forceinline__ F3 slab_recip(const Ray& r) {
 // such broadcasts as register copies, and 9 extra VGPRs spill); hence inline asm, one
 // step per statement so the six (axis, plane) chains of a node issue stage by stage.
 typedef float v2f __attribute__((ext_vector_type(2)));
-template <int S> __device__ __forceinline__ v2f pk_sub(v2f b, v2f O) {   // a = b - o
+// SB != 0: the box pair is wave-uniform and sits in SGPRs (the wave-uniform prologue's record, which
+// the scalar cache delivered) and is read from there, with no copy of the record into VGPRs.
+// SB 1: as the packed op's src0, an SGPR pair: one constant-bus operand, both halves read as a pair
+// (scripts/micro/pk_sgpr.hip checks that on the GPU).  SB 2 (the depth-1 kernels): each value as src0
+// of a plain v_sub_f32, the same IEEE result as the packed op's half, and pk_mulb's plain twin
+// multiplies: 24 instructions for 12, and yet the faster form there (C3 0.2315 vs 0.2374 ms per frame,
+// DESIGN.md 7.5); the other kernels gain scratch from it and keep the packed one.
+template <int S, int SB = 0> __device__ __forceinline__ v2f pk_sub(v2f b, v2f O) {   // a = b - o
     v2f a;
+    if (SB == 2) {
+        const float o = S ? O.y : O.x;
+        asm("v_sub_f32 %0, %1, %2" : "=v"(a.x) : "s"(b.x), "v"(o));
+        asm("v_sub_f32 %0, %1, %2" : "=v"(a.y) : "s"(b.y), "v"(o));
+        return a;
+    }
+    if (SB == 1) {
+        if (S) asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(a) : "s"(b), "v"(O));
+        else   asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(a) : "s"(b), "v"(O));
+        return a;
+    }
     if (S) asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(a) : "v"(b), "v"(O));
     else   asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(a) : "v"(b), "v"(O));
     return a;
 }
-template <int S> __device__ __forceinline__ v2f pk_mulb(v2f a, v2f Y) {  // q = a * y
+template <int S, int SB = 0> __device__ __forceinline__ v2f pk_mulb(v2f a, v2f Y) {  // q = a * y
     v2f q;
+    if (SB == 2) {
+        const float y = S ? Y.y : Y.x;
+        asm("v_mul_f32 %0, %1, %2" : "=v"(q.x) : "v"(a.x), "v"(y));
+        asm("v_mul_f32 %0, %1, %2" : "=v"(q.y) : "v"(a.y), "v"(y));
+        return q;
+    }
     if (S) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(q) : "v"(a), "v"(Y));
     else   asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(q) : "v"(a), "v"(Y));
     return q;
@@ -125,16 +149,16 @@ __device__ __forceinline__ RayPk ray_pk(const F3& o, const F3& d, const F3& y) {
 // d > 0 orders the two slab values as the box's planes and d < 0 the other way round: min(a, b) is
 // a or b itself, and n and f are one v_max3 / v_min3 each, 4 VALU per visit instead of 16.  Which
 // of two equal values comes out (+-0 included) may differ; everything downstream only compares.
-template <bool ZERO = true, int OCT = -1>
+template <bool ZERO = true, int OCT = -1, int SB = 0>
 __device__ __forceinline__ void slab2_pk(const float4& q0, const float4& q1, const float4& q2, const RayPk& R,
                                          float& n0, float& f0, float& n1, float& f1) {
     // x: o, d, y = lo halves of R.oxy / R.dxy / R.yxy; y: the hi halves; z: lo / hi of R.ozdz, lo of R.yz
-    const v2f a0 = pk_sub<0>(v2f{q0.x, q0.y}, R.oxy), a1 = pk_sub<0>(v2f{q0.z, q0.w}, R.oxy);
-    const v2f a2 = pk_sub<1>(v2f{q1.x, q1.y}, R.oxy), a3 = pk_sub<1>(v2f{q1.z, q1.w}, R.oxy);
-    const v2f a4 = pk_sub<0>(v2f{q2.x, q2.y}, R.ozdz), a5 = pk_sub<0>(v2f{q2.z, q2.w}, R.ozdz);
-    const v2f m0 = pk_mulb<0>(a0, R.yxy), m1 = pk_mulb<0>(a1, R.yxy);
-    const v2f m2 = pk_mulb<1>(a2, R.yxy), m3 = pk_mulb<1>(a3, R.yxy);
-    const v2f m4 = pk_mulb<0>(a4, R.yz), m5 = pk_mulb<0>(a5, R.yz);
+    const v2f a0 = pk_sub<0, SB>(v2f{q0.x, q0.y}, R.oxy), a1 = pk_sub<0, SB>(v2f{q0.z, q0.w}, R.oxy);
+    const v2f a2 = pk_sub<1, SB>(v2f{q1.x, q1.y}, R.oxy), a3 = pk_sub<1, SB>(v2f{q1.z, q1.w}, R.oxy);
+    const v2f a4 = pk_sub<0, SB>(v2f{q2.x, q2.y}, R.ozdz), a5 = pk_sub<0, SB>(v2f{q2.z, q2.w}, R.ozdz);
+    const v2f m0 = pk_mulb<0, SB>(a0, R.yxy), m1 = pk_mulb<0, SB>(a1, R.yxy);
+    const v2f m2 = pk_mulb<1, SB>(a2, R.yxy), m3 = pk_mulb<1, SB>(a3, R.yxy);
+    const v2f m4 = pk_mulb<0, SB>(a4, R.yz), m5 = pk_mulb<0, SB>(a5, R.yz);
     v2f ax, bx, ay, by, az, bz;
     if (kMath == 2) {   // S_ref: a * Y is the quotient (see above)
         ax = m0; bx = m1; ay = m2; by = m3; az = m4; bz = m5;
@@ -321,8 +345,8 @@ template <bool GUARD> __device__ __forceinline__ int slot_put(int get_at, int co
     return GUARD ? get_at + 256 : col0 + max((int)(sb - kStackBase) - 256, 0);
 }
 
-// put_at: the LDS address of slot sc - 2
-template <int MODE, int OCT = -1>
+// put_at: the LDS address of slot sc - 2.  SB: the record is wave-uniform, in SGPRs (pk_sub).
+template <int MODE, int OCT = -1, int SB = 0>
 __device__ __forceinline__ void inner_step(const float4& q0, const float4& q1, const float4& q2, float2 refs,
                                            const RayPk& rp, float th, uint32_t popped, int put_at,
                                            uint32_t& cur, uint32_t& nxt, uint32_t& sb) {
@@ -330,7 +354,7 @@ __device__ __forceinline__ void inner_step(const float4& q0, const float4& q1, c
     if (MODE == 2) {
         slab2_div(q0, q1, q2, F3{rp.oxy.x, rp.oxy.y, rp.ozdz.x}, F3{rp.dxy.x, rp.dxy.y, rp.ozdz.y}, n0, f0, n1, f1);
     } else {
-        slab2_pk<MODE == 1, MODE == 0 ? OCT : -1>(q0, q1, q2, rp, n0, f0, n1, f1);
+        slab2_pk<MODE == 1, MODE == 0 ? OCT : -1, SB>(q0, q1, q2, rp, n0, f0, n1, f1);
     }
     // (n <= f) && (n <= th) == n <= min(f, th) for every input: th is a finite hit distance, and n
     // and f are NaN together or not at all (per axis the NaN-ignoring min and max of the two slab
@@ -375,6 +399,16 @@ __device__ __forceinline__ float2 rec_load2(__amdgpu_buffer_rsrc_t r, uint32_t o
 template <bool CLOSEST, int MODE, int TR, bool SEL = false, bool GUARD = true, int OCT = -1>
 __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, float& tHit, const Stack& st,
                                               int& result) {
+    // The trimmed trip (DESIGN.md 7.2) is the depth-1 kernels' (SEL): the uniform prologue loop and the
+    // lean main-loop head (kLean: offset select next to the leaf compare, child refs loaded inside the
+    // inner step's region), the slab test on scalar operands (kScalarBox 2) and the shift-add decode
+    // (kShiftDecode).  The wavefront and query kernels keep the earlier forms of
+    // all of them: they run slower with the lean head (C5 0.738 vs 0.703 ms per frame) and gain scratch
+    // from every partial combination.  The fused kernel (GUARD false: 7 waves' registers, already in
+    // scratch) takes the scalar box operands in their packed form and the decode, with which it loses
+    // 4 B of scratch; the uniform loop or the lean head cost it 4 B.
+    constexpr bool kLean = SEL, kShiftDecode = SEL || !GUARD;
+    constexpr int kScalarBox = MODE == 2 ? 0 : SEL ? 2 : GUARD ? 0 : 1;   // pk_sub's SB
     const int col0 = (int)(uint32_t)(uintptr_t)(lds_u32*)st.lds;   // the column's entry 0, as an LDS byte address
     const RayPk rp = ray_pk(ray_io.ori, ray_io.dir, slab_recip(ray_io));
     // the packed reciprocal goes back as inv_dir: RN(1/d) itself in S_strict / S_hw, the
@@ -391,6 +425,11 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
     // the lane has just arrived at, and the main loop decodes it at the top of its next trip,
     // the one place that does (the root, a child, or what a pop brought back).
     uint32_t tk = 0, tend = 0;
+    // The decode's one scene field.  The depth-1 kernels (SEL) hold it in a VGPR through the loops: as
+    // one of the scene's SGPRs it is spilled around them and comes back by v_readlane_b32, its whole
+    // four-register tuple, on every arrival.
+    uint32_t tri_off = S.tri_off;
+    if (SEL && kOctLoops) asm("" : "+v"(tri_off));
     // inner and triangle records share one allocation: buffer loads at a 32-bit byte offset
     // from one descriptor (no 64-bit address arithmetic per iteration)
     const __amdgpu_buffer_rsrc_t recs =
@@ -406,9 +445,9 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
     typedef const __attribute__((address_space(4))) su4 csu4;
     typedef const __attribute__((address_space(4))) su2 csu2;
     if (TR == 2 && CLOSEST) rtk::timeline_mark(st.fc, 6);   // the closest-hit traversal starts
-    while ((int)sb >= (int)kStackBase) {
-        const uint32_t c0 = __builtin_amdgcn_readfirstlane(cur);
-        if (__builtin_amdgcn_ballot_w64(cur != c0) != 0 || (c0 & kLeafBit)) break;
+    // One prologue step of the lanes in exec, all on inner node c0: the record comes in SGPRs and
+    // the slab test reads it from there (pk_sub's SB; the division form is plain C++).
+    const auto uniform_step = [&](uint32_t c0) __attribute__((always_inline)) {
         const int at = slot_get<GUARD>(col0, sb);
         const uint32_t popped = lds_get(at);
         if (TR == 1) rtk::fetch_count(st.fc, false, cur, false);
@@ -420,43 +459,88 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
         const float4 q1 = make_float4(__uint_as_float(u1.x), __uint_as_float(u1.y), __uint_as_float(u1.z), __uint_as_float(u1.w));
         const float4 q2 = make_float4(__uint_as_float(u2.x), __uint_as_float(u2.y), __uint_as_float(u2.z), __uint_as_float(u2.w));
         const float2 q3 = make_float2(__uint_as_float(u3.x), __uint_as_float(u3.y));
-        inner_step<MODE, OCT>(q0, q1, q2, q3, rp, th, popped, slot_put<GUARD>(at, col0, sb), cur, nxt, sb);
+        inner_step<MODE, OCT, kScalarBox>(q0, q1, q2, q3, rp, th, popped, slot_put<GUARD>(at, col0, sb), cur, nxt, sb);
+    };
+    if (kLean) {
+        // The loop itself is wave-uniform (scalar branches only): a per-lane loop condition makes the
+        // compiler fold every exit, the uniform ones too, into exec-mask arithmetic on every trip.
+        // Lanes that have finished (they never come back) sit out the step's one exec region; c0 is
+        // the node of the first lane still in the loop, and one compare serves both exit tests: with
+        // its leaf bit cleared a leaf c0 differs from that lane's own `cur`.
+        for (;;) {
+            const bool live = (int)sb >= (int)kStackBase;
+            const uint64_t lm = __builtin_amdgcn_ballot_w64(live);
+            if (lm == 0) break;
+            const uint32_t c0 = __builtin_amdgcn_readlane(cur, __builtin_ctzll(lm));
+            if ((__builtin_amdgcn_ballot_w64(cur != (c0 & ~kLeafBit)) & lm) != 0) break;
+            // (keeps the compiler from merging the uniform exit with the per-lane condition below
+            // into one divergent branch, which brings the mask arithmetic back)
+            asm volatile("");
+            if (live) uniform_step(c0);
+        }
+    } else {
+        while ((int)sb >= (int)kStackBase) {
+            const uint32_t c0 = __builtin_amdgcn_readfirstlane(cur);
+            if (__builtin_amdgcn_ballot_w64(cur != c0) != 0 || (c0 & kLeafBit)) break;
+            uniform_step(c0);
+        }
     }
     if (TR == 2 && CLOSEST) rtk::timeline_mark(st.fc, 7);   // its wave-uniform prologue is over
     while ((int)sb >= (int)kStackBase) {
         const bool leaf = (cur & kLeafBit) != 0;
-        if (leaf && tk >= tend) leaf_bytes(S, cur, tk, tend);
+        // SEL (the depth-1 kernel): a select between the two byte offsets, so the loads issue
+        // without an exec-masked branch in front of them (C3 -1.4 %, C4 -1.6 %; the wavefront
+        // kernels are faster with the branch, C5 +1.2 %: DESIGN.md 6.2).  tk is already a
+        // byte offset: no multiply (a 24-bit one here was wrong from 2^24 records on).
+        // The select stands next to the leaf compare, whose mask it then reads as it is (a ballot
+        // in a later block is rebuilt from a 0 / 1 VGPR: two VALU more on the way to the loads); a
+        // lane that arrives on its leaf takes the offset from the decode instead.
+        uint32_t off = 0;
+        const auto select_off = [&]() __attribute__((always_inline)) {
+            if (SEL) {
+                asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(off) : "v"(cur << 6), "v"(tk), "s"(__builtin_amdgcn_ballot_w64(leaf)));
+            } else {
+                off = leaf ? tk : cur << 6;
+            }
+        };
+        if (kLean) select_off();
+        if (leaf && tk >= tend) {
+            leaf_bytes<kShiftDecode>(S, tri_off, cur, tk, tend);
+            off = tk;
+        }
+        if (!kLean) select_off();
         const int at = slot_get<GUARD>(col0, sb);
         const uint32_t popped = lds_get(at);
         // TR 1 (measurement instantiation only, rt_fetch_counts): this iteration's fetches counted;
         // TR 2 (rt_wave_timeline): the wave's loop trips counted
         if (TR == 1) rtk::fetch_count(st.fc, leaf, leaf ? (0x80000000u | tk) : cur);
         if (TR == 2) rtk::timeline_step(st.fc, CLOSEST ? 0 : 2);
-        // SEL (the depth-1 kernel): a select between the two byte offsets, so the loads issue
-        // without an exec-masked branch in front of them (C3 -1.4 %, C4 -1.6 %; the wavefront
-        // kernels are faster with the branch, C5 +1.2 %: DESIGN.md 6.2).  tk is already a
-        // byte offset: no multiply (a 24-bit one here was wrong from 2^24 records on).
-        uint32_t off;
-        if (SEL) {
-            asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(off) : "v"(cur << 6), "v"(tk), "s"(__builtin_amdgcn_ballot_w64(leaf)));
-        } else {
-            off = leaf ? tk : cur << 6;
-        }
         uint32_t t_issue = 0;
         if (TR == 2 && RTK_TL_SPLIT) t_issue = (uint32_t)__builtin_amdgcn_s_memrealtime();
         const float4 q0 = rec_load4(recs, off), q1 = rec_load4(recs, off + 16u), q2 = rec_load4(recs, off + 32u);
-        // The child refs are loaded right after the boxes, by the inner lanes only (an
-        // exec-masked load); the barrier keeps the compiler from sinking the load into the
-        // inner-step branch, where a mixed iteration would issue it only after the triangle
-        // lanes' wait for their record: a second round trip.
-        float2 q3 = make_float2(0.0f, 0.0f);
-        if (!leaf) q3 = rec_load2(recs, off + 48u);
-        asm volatile("" ::: "memory");
+        // The child refs are loaded by the inner lanes only, as the first instruction of the inner
+        // step's exec region, which precedes the triangle step in program order: in a mixed
+        // iteration the load is out before any wait of that trip (one round trip per trip; the
+        // scheduling barrier keeps it in front of the slab test's first wait).  Leaf lanes never
+        // read q3.  The earlier form (every kernel without SEL; the timeline's split diagnostic, which waits
+        // for all four loads before either step): a masked load in a region of its own right after the
+        // boxes, and a barrier that keeps the compiler from sinking it behind the triangle lanes' wait.
+        constexpr bool kRefsEarly = (TR == 2 && RTK_TL_SPLIT) || !kLean;
+        float2 q3;
+        if (kRefsEarly) {
+            q3 = make_float2(0.0f, 0.0f);
+            if (!leaf) q3 = rec_load2(recs, off + 48u);
+            asm volatile("" ::: "memory");
+        }
         if (TR == 2 && RTK_TL_SPLIT) {   // diagnostic: the trip's memory wait (all four loads in)
             asm volatile("" ::"v"(q0.x), "v"(q1.x), "v"(q2.x), "v"(q3.x));
             rtk::timeline_wait(st.fc, CLOSEST ? 0 : 1, (uint32_t)__builtin_amdgcn_s_memrealtime() - t_issue);
         }
         if (!leaf) {
+            if (!kRefsEarly) {
+                q3 = rec_load2(recs, off + 48u);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             inner_step<MODE, OCT>(q0, q1, q2, q3, rp, th, popped, slot_put<GUARD>(at, col0, sb), cur, nxt, sb);
         } else {
             // Moller-Trumbore on one reference of the leaf, in order (:965-997).  An empty leaf

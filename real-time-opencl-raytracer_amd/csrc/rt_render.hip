@@ -271,11 +271,25 @@ __device__ __forceinline__ void leaf_range(const DevScene& S, uint32_t ref, int&
 
 // The same range as byte offsets of the records in the fast traversal's allocation
 // (triangle records after the inner records, 48 B each): [tk, tend).
-__device__ __forceinline__ void leaf_bytes(const DevScene& S, uint32_t ref, uint32_t& tk, uint32_t& tend) {
+// SHIFT (the depth-1 kernels): 48 x = (3 x) << 4 in two full-rate shift-adds, for any 32-bit x (an
+// offset has 26 bits, an escape leaf's count is bounded only by the allocation: no 24-bit multiply);
+// written out because the compiler turns the C++ of it into two v_mad_u64_u32 with a 64-bit addend
+// (DESIGN.md 7.2), which the other kernels keep: the four shift-adds cost them scratch.
+// tri_off: S.tri_off as the caller holds it (a VGPR copy where the scene's SGPRs do not survive the loop).
+template <bool SHIFT>
+__device__ __forceinline__ void leaf_bytes(const DevScene& S, uint32_t tri_off, uint32_t ref, uint32_t& tk, uint32_t& tend) {
     int off, cnt;
     leaf_range(S, ref, off, cnt);
-    tk = S.tri_off + (uint32_t)off * 48u;
-    tend = tk + (uint32_t)cnt * 48u;
+    if (!SHIFT) {
+        tk = tri_off + (uint32_t)off * 48u;
+        tend = tk + (uint32_t)cnt * 48u;
+        return;
+    }
+    uint32_t o3, c3;
+    asm("v_lshl_add_u32 %0, %1, 1, %1" : "=v"(o3) : "v"(off));
+    asm("v_lshl_add_u32 %0, %1, 1, %1" : "=v"(c3) : "v"(cnt));
+    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(tk) : "v"(o3), "v"(tri_off));
+    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(tend) : "v"(c3), "v"(tk));
 }
 
 struct Stack {

@@ -126,6 +126,13 @@ static long long q_vec = 0, q_vec_inner = 0, q_vec_tri = 0, lanes_vec = 0, iters
 static long long q_rank[4];   // inner vector quad requests with bfs rank < 256, 512, 1024, 4096
 static const int KR[4] = {256, 512, 1024, 4096};
 static long long t2_second = 0, lane_steps = 0;   // every lane step of the main loop and the prologue
+// env COST="P,H,I,L,D": trips by kind and a per-block instruction cost (DESIGN.md 7.2's table).  A
+// prologue trip costs P; a main-loop trip costs H (head + tail, every trip), + I when a lane takes an
+// inner step, + L when a lane takes a triangle step, + D when a lane arrives on a leaf in that trip
+// (the decode at the top).  COST=1: the parent listing's 89,36,44,63,18.
+static int COST = 0, CP = 89, CH = 36, CI = 44, CL = 63, CD = 18;
+static long long k_inner_only = 0, k_leaf_only = 0, k_mixed = 0, k_arrive = 0, k_leaf_lanes = 0;
+static int arrived[64];   // the lane reached a leaf it has not begun (set after its step, spent at the next trip)
 
 static void run_wave(lane* L, int* act) {
     // prologue: while all active lanes sit on the same inner node
@@ -136,12 +143,19 @@ static void run_wave(lane* L, int* act) {
         iters_pro++;
         for (int i = 0; i < 64; ++i) if (act[i] && L[i].sc > 0) { lane_step(&L[i]); lane_steps++; }
     }
+    // a lane that enters the main loop on a leaf (the root, or a child the prologue's last trip chose) arrives there
+    for (int i = 0; i < 64; ++i) arrived[i] = act[i] && L[i].sc > 0 && N[L[i].stack[L[i].sc - 1]].l < 0;
     for (;;) {
         int any = 0;
         int rec[64];
         for (int i = 0; i < 64; ++i) { rec[i] = 0x7fffffff; if (act[i] && L[i].sc > 0) { any = 1; rec[i] = lane_record(&L[i]); } }
         if (!any) break;
         iters++;
+        if (COST) {
+            int ni = 0, nl = 0, na = 0;
+            for (int i = 0; i < 64; ++i) if (rec[i] != 0x7fffffff) { if (rec[i] >= 0) ni++; else { nl++; na += arrived[i]; } arrived[i] = 0; }
+            k_inner_only += ni && !nl; k_leaf_only += nl && !ni; k_mixed += ni && nl; k_arrive += na > 0; k_leaf_lanes += nl;
+        }
         for (int q = 0; q < 16; ++q) {
             int seen[4], ns = 0;
             for (int j = 0; j < 4; ++j) {
@@ -172,6 +186,10 @@ static void run_wave(lane* L, int* act) {
             const int leaf0 = L[i].stack[L[i].sc - 1];
             const int in_leaf = N[leaf0].l < 0;
             lane_step(&L[i]); lane_steps++;
+            if (COST && L[i].sc > 0) {   // on a leaf it has not begun: a new `cur`, or the same leaf popped back to
+                const int c1 = L[i].stack[L[i].sc - 1];
+                arrived[i] = N[c1].l < 0 && (c1 != leaf0 || !in_leaf);
+            }
             if (help && in_leaf)
                 for (int k = 1; k < HELP_G && L[i].sc > 0 && L[i].stack[L[i].sc - 1] == leaf0 && L[i].tk < L[i].tend; ++k) {
                     lane_step(&L[i]); helped_extra++;
@@ -190,6 +208,7 @@ int main(int argc, char** argv) {
     CULL = getenv("CULL") ? atoi(getenv("CULL")) : 0;
     HELP = getenv("HELP") ? atoi(getenv("HELP")) : 0;
     HELP_G = getenv("HELP_G") ? atoi(getenv("HELP_G")) : 4;
+    if (getenv("COST")) { COST = 1; sscanf(getenv("COST"), "%d,%d,%d,%d,%d", &CP, &CH, &CI, &CL, &CD); if (!strchr(getenv("COST"), ',')) CP = 89; }
     size_t s;
     N = (node*)rd("c3_nodes.bin", &s); NN = (int)(s / sizeof(node));
     V = (float*)rd("c3_vertices.bin", 0); IDX = (int32_t*)rd("c3_indices.bin", 0); REF = (int32_t*)rd("c3_tri_indices.bin", 0);
@@ -249,6 +268,20 @@ int main(int argc, char** argv) {
     if (T2 || TT2) printf("T2: second inner steps taken without a fetch: %lld\n", t2_second);
     if (CULL) printf("CULL=%d: popped inner entries skipped %lld\n", CULL, culled);
     if (HELP) printf("HELP=%d (groups of %d): triangle tests taken by helper lanes %lld\n", HELP, HELP_G, helped_extra);
+    if (COST) {
+        const long long wi = k_inner_only + k_mixed, wl = k_leaf_only + k_mixed;
+        const double cp = (double)CP * iters_pro, ch = (double)CH * iters, ci = (double)CI * wi, cl = (double)CL * wl,
+                     cd = (double)CD * k_arrive, tot = cp + ch + ci + cl + cd;
+        printf("COST %d,%d,%d,%d,%d: main-loop trips inner-only %lld, leaf-only %lld, mixed %lld; leaf lanes per leaf trip %.1f\n",
+               CP, CH, CI, CL, CD, k_inner_only, k_leaf_only, k_mixed, wl ? (double)k_leaf_lanes / wl : 0.0);
+        printf("  | part | trips | instructions per trip | share of loop instructions |\n  |---|---|---|---|\n");
+        printf("  | wave-uniform prologue | %lld | %d | %.1f %% |\n", iters_pro, CP, 100.0 * cp / tot);
+        printf("  | main loop, head + tail | %lld | %d | %.1f %% |\n", iters, CH, 100.0 * ch / tot);
+        printf("  | inner block | %lld | %d | %.1f %% |\n", wi, CI, 100.0 * ci / tot);
+        printf("  | leaf blocks | %lld | %d | %.1f %% |\n", wl, CL, 100.0 * cl / tot);
+        printf("  | leaf arrival decode | %lld | %d | %.1f %% |\n", k_arrive, CD, 100.0 * cd / tot);
+        printf("  modelled loop instructions per frame: %.0f\n", tot);
+    }
     printf("rays whose stack outgrew 16 LDS entries: %lld\n", deep_lanes);
     printf("iters %lld prologue %lld  lane fetches(vec) %lld  quad req %lld (inner %lld tri %lld) lanes/qreq %.3f\n",
            iters, iters_pro, lanes_vec, q_vec, q_vec_inner, q_vec_tri, (double)lanes_vec / q_vec);
