@@ -566,6 +566,44 @@ int rt_trace_rays(rt_ctx* ctx, const rt_ray* rays, int64_t n, uint32_t flags, rt
 int rt_trace_rays_device(rt_ctx* ctx, const rt_ray* d_rays, int64_t n, uint32_t flags, rt_hit* d_hits, void* stream);
 int rt_last_query_timing(rt_ctx* ctx, float* ms);
 
+/* Ray queries with hit attributes: the same query, answered with a 64-byte record per
+ * ray that says where on the triangle the ray landed and which way the surface faces, defined as what
+ * the frame's own shading computes at that hit, in the arithmetic the flags select.
+ *
+ * Rays, the validity rule, flags (RT_FLAG_ANY_HIT included), refusals, n == 0, synchrony, slot and
+ * stream behaviour are rt_trace_rays[_device]'s, word for word; rt_last_query_timing, rt_last_deferred
+ * and rt_overflow_count cover this query as they cover the plain one.  d_hits must be 16-byte aligned
+ * (RT_ERR_INVALID_ARG before any GPU work otherwise).
+ *
+ * id and t are exactly rt_hit's for that ray and those flags.  For a hit, with ori and dir those of
+ * ray_init(o, d), p0 p1 p2 the corners and n0 n1 n2 the normals of triangle id / 3 (vertices[indices[id
+ * + k]], normals[normals_indices[id + k]], as the last upload, build or vertex update left them), e1 =
+ * p1 - p0 and e2 = p2 - p0:
+ *   u, v    the Moller-Trumbore barycentrics by the traversal's own lines (volumeRender.cl:257-282):
+ *           the hit is (1 - u - v) p0 + u p1 + v p2;
+ *   p       ori + dir * (t - 0.001f): the frame's hit point, 0.001 SHORT of the surface along the ray
+ *           (volumeRender.cl:1306-1403), from which it starts its reflection and shadow rays;
+ *   ng      normalize(cross(e1, e2)): the geometric normal by the winding, NOT turned towards the ray;
+ *   ndotd   dot(ng, dir): negative where the ray met the front face;
+ *   ns      the frame's shading normal at p: normalize of the vertex normals interpolated by the
+ *           reference's Cramer barycentrics (volumeRender.cl:27-53), bit for bit what the render path
+ *           shades with, whatever that is for degenerate normals.
+ * With RT_FLAG_ANY_HIT the attributes are those of the triangle the traversal accepted.
+ * A miss (no hit, an invalid ray, tmax <= 0.001f, a stack overflow) is id = -1, t = the ray's tmax
+ * word and the other 14 words zero.  reserved0 and reserved1 are written 0.
+ * Albedo and material are not in the record: id / 3 indexes the caller's own tri_to_material. */
+typedef struct rt_hit_attr {
+    int32_t id; float t, u, v;
+    float px, py, pz, ndotd;
+    float ngx, ngy, ngz; uint32_t reserved0;
+    float nsx, nsy, nsz; uint32_t reserved1;
+} rt_hit_attr;                                                                                  /* 64 B */
+#ifdef __cplusplus
+static_assert(sizeof(rt_hit_attr) == 64, "rt_hit_attr is 64 bytes");
+#endif
+int rt_trace_rays_attr(rt_ctx* ctx, const rt_ray* rays, int64_t n, uint32_t flags, rt_hit_attr* hits);
+int rt_trace_rays_attr_device(rt_ctx* ctx, const rt_ray* d_rays, int64_t n, uint32_t flags, rt_hit_attr* d_hits, void* stream);
+
 /* Traversals of the last frame (or of the last ray query, if that came later) that outgrew the
  * fast kernel's LDS stack and restarted in-kernel with the general traversal (same result,
  * slower ray); diagnostics, synchronizes the stream. */

@@ -180,6 +180,18 @@ __device__ __forceinline__ float ray_tri(const Ray& r, F3 v0, F3 e1, F3 e2) {
     return dot(e2, qvec) * det;
 }
 
+// ray_tri's u and v, by its own lines without its early-outs (rt_trace_rays_attr):
+// the hit is (1 - u - v) v0 + u (v0 + e1) + v (v0 + e2)
+__device__ __forceinline__ void ray_tri_uv(const Ray& r, F3 v0, F3 e1, F3 e2, float& u, float& v) {
+    F3 tvec = r.ori - v0;
+    F3 pvec = cross(r.dir, e2);
+    float det = dot(e1, pvec);
+    det = rcp_(det);
+    u = dot(tvec, pvec) * det;
+    F3 qvec = cross(tvec, e1);
+    v = dot(r.dir, qvec) * det;
+}
+
 // volumeRender.cl:27-53: Cramer barycentrics on absolute positions.
 //   D = p0.x*(A) - p1.x*(B) + p2.x*(C), each (..) = u*v - w*z
 // S_ref contraction: (u*v - w*z) -> fma(u, v, -(w*z)); the outer
@@ -208,6 +220,28 @@ __device__ __forceinline__ F3 normal_at(F3 pn, F3 p0, F3 p1, F3 p2, F3 n0, F3 n1
                   mad_(l2, n2.z, mad_(l0, n0.z, m.z))};
     }
     return (l0 * n0 + l1 * n1) + l2 * n2;
+}
+
+// What a ray query reports about a hit besides id and t (rt_hit_attr), from the
+// corners and normals of the triangle's shading record: u, v by ray_tri's lines on e1 = p1 - p0,
+// e2 = p2 - p0; p and ns are shade_hit's vNew (0.001 short of the surface along the ray) and its
+// `normal`, by the same calls; ng = normalize(cross(e1, e2)) is not turned towards the ray, and
+// ndotd = dot(ng, dir) < 0 says that the ray met the front face.
+struct HitAttr {
+    float u, v;
+    F3 p;
+    float ndotd;
+    F3 ng, ns;
+};
+__device__ __forceinline__ HitAttr hit_attr(const Ray& ray, float t, F3 p0, F3 p1, F3 p2, F3 n0, F3 n1, F3 n2) {
+    HitAttr h;
+    const F3 e1 = p1 - p0, e2 = p2 - p0;
+    ray_tri_uv(ray, p0, e1, e2, h.u, h.v);
+    h.p = mad3(ray.dir, t - 0.001f, ray.ori);   // r.ori + r.dir * (t - 0.001f)
+    h.ng = normalize(cross(e1, e2));
+    h.ndotd = dot(h.ng, ray.dir);
+    h.ns = normalize(normal_at(h.p, p0, p1, p2, n0, n1, n2));
+    return h;
 }
 
 // volumeRender.cl:1732-1779

@@ -1133,4 +1133,75 @@ __global__ void __launch_bounds__(256, kMath == 2 ? RTK_QUERY_REF_WAVES : RTK_QU
     }
 }
 
+// ============================================================================
+// Ray queries with hit attributes (rt_trace_rays_attr, DESIGN.md 19): query_kernel's grid, ray
+// loads, validity test, trace<> instantiation, restart value and spill columns, and after the
+// traversal a lane that hit reads the seven 16-B words of triangle id / 3's shading record and
+// computes hit_attr (rt_device_math.h): what shade_hit computes at that hit.  A record is four
+// 16-B words {id, t, u, v} {p, ndotd} {ng, 0} {ns, 0}; a miss is {-1, tmax word, 0 ...}.
+// The wave stages its 64 records in the 16 stack rows of its LDS columns (exactly 4 KiB; free once
+// trace<> has returned, and a traversal expects nothing of what they hold when it starts; the
+// guard rows below them are not touched) and stores them as four contiguous 1-KiB wave stores.
+// The rows are the wave's own, so it waits for its LDS writes and needs no barrier.  (Each lane
+// storing its own four words, 64 B apart from its neighbour's, measured 2 to 5 % slower: C3's
+// primary rays in S_ref 0.237 / 0.244 against 0.232 / 0.232 ms, incoherent rays 0.997 / 0.994
+// against 0.971 / 0.972, DESIGN.md 19.)
+// Q.hits is the rt_hit_attr buffer here (16-byte aligned).
+// ============================================================================
+template <bool ANY, bool FASTONLY>
+__global__ void __launch_bounds__(256, kMath == 2 ? RTK_QATTR_REF_WAVES : RTK_QATTR_WAVES) query_attr_kernel(DevScene S, Outputs O, rtk::Query Q) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_stack[4][rtk::kLdsRows][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t ngroups = (Q.n + rtk::kSegRays - 1) / rtk::kSegRays;
+    uint32_t home = blockIdx.x & (rtk::kCursors - 1u);
+    Stack st;
+    st.lds = &s_stack[wave][rtk::kLdsGuard][lane];
+    st.glb = O.gstack + ((size_t)blockIdx.x * rtk::kBlockThreads + threadIdx.x);
+    st.gstride = O.local_pixels;   // the lanes launched
+    uint4* const out = (uint4*)Q.hits;
+    for (;;) {
+        const uint32_t g = rtk::grab_group(Q.fetch, ngroups, home);
+        if (g == rtk::kNoGroup) break;
+        const uint32_t i = g * rtk::kSegRays + (uint32_t)lane;
+        const bool inside = i < Q.n;   // (false only in the last group's tail)
+        float4 a = make_float4(0, 0, 0, 0), b = a;
+        if (inside) {
+            const float4* rp = Q.rays + (size_t)i * 2;
+            a = rp[0];
+            b = rp[1];
+        }
+        uint4 r0 = make_uint4(0xFFFFFFFFu, __float_as_uint(a.w), 0u, 0u), r1 = make_uint4(0u, 0u, 0u, 0u), r2 = r1, r3 = r1;
+        bool overflow = false;
+        if (inside && query_ray_ok(a, b)) {
+            Ray ray = ray_init(F3{a.x, a.y, a.z}, F3{b.x, b.y, b.z});
+            float t = a.w;
+            const int hit = trace<!ANY, FASTONLY, 0, true, true, kOctLoops>(S, O, ray, t, st, overflow, a.w);
+            if (hit >= 0) {
+                const float4* sp = S.shade + (size_t)(hit / 3) * 7;
+                const float4 p0 = sp[0], p1 = sp[1], p2 = sp[2], m0 = sp[3], m1 = sp[4], m2 = sp[5];
+                const HitAttr h = hit_attr(ray, t, xyz(p0), xyz(p1), xyz(p2), xyz(m0), xyz(m1), xyz(m2));
+                r0 = make_uint4((uint32_t)hit, __float_as_uint(t), __float_as_uint(h.u), __float_as_uint(h.v));
+                r1 = make_uint4(__float_as_uint(h.p.x), __float_as_uint(h.p.y), __float_as_uint(h.p.z), __float_as_uint(h.ndotd));
+                r2 = make_uint4(__float_as_uint(h.ng.x), __float_as_uint(h.ng.y), __float_as_uint(h.ng.z), 0u);
+                r3 = make_uint4(__float_as_uint(h.ns.x), __float_as_uint(h.ns.y), __float_as_uint(h.ns.z), 0u);
+            }
+        }
+        uint4* const stage = (uint4*)&s_stack[wave][rtk::kLdsGuard][0];   // 256 words of 16 B: record l at 4 l
+        stage[lane * 4 + 0] = r0;
+        stage[lane * 4 + 1] = r1;
+        stage[lane * 4 + 2] = r2;
+        stage[lane * 4 + 3] = r3;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        const uint32_t left = min(Q.n - g * rtk::kSegRays, rtk::kSegRays) * 4u;   // 16-B words of this group that exist
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint32_t j = k * 64u + (uint32_t)lane;
+            const uint4 w = stage[j];
+            if (j < left) out[(size_t)g * 256u + j] = w;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // read out before the next traversal writes the rows
+        if (overflow) atomicAdd(O.overflow, 1ull);
+    }
+}
+
 }  // namespace RTK_NS

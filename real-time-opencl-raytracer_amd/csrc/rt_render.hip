@@ -79,6 +79,12 @@
 #ifndef RTK_QUERY_WAVES
 #define RTK_QUERY_WAVES 7       // the same for S_strict / S_hw, as their other kernels
 #endif
+#ifndef RTK_QATTR_REF_WAVES
+#define RTK_QATTR_REF_WAVES 8   // waves per SIMD the S_ref attribute query kernels are bounded to (no scratch: DESIGN.md 19)
+#endif
+#ifndef RTK_QATTR_WAVES
+#define RTK_QATTR_WAVES 7       // the same for S_strict / S_hw
+#endif
 #ifndef RTK_QUERY_GRID_PCT
 #define RTK_QUERY_GRID_PCT 75   // persistent query grid, percent of the blocks the chip holds at once (C3's 2.07 M primary
                                 // rays, closest hit / incoherent rays: 50 % 0.248 / 0.955 ms, 75 % 0.232 / 0.998, 100 % 0.242 /
@@ -1094,7 +1100,7 @@ struct rt_ctx {
     int wf_grid[3] = {0, 0, 0};   // persistent wavefront grid per math mode
     // ray queries: the persistent grid per math mode, the host form's staging, and the
     // slot of the last query while no frame has come after it (rt_last_deferred, rt_last_query_timing)
-    int query_grid[3] = {0, 0, 0};
+    int query_grid[2][3] = {{0, 0, 0}, {0, 0, 0}};   // [record kind][math]
     float4* d_qrays = nullptr; size_t qrays_cap = 0;
     uint2* d_qhits = nullptr; size_t qhits_cap = 0;
     FrameSlot* query_slot = nullptr;
@@ -1383,6 +1389,10 @@ template <int M> struct Kernels;
             return any ? (fast ? (void*)NS::query_kernel<true, true> : (void*)NS::query_kernel<true, false>) \
                        : (fast ? (void*)NS::query_kernel<false, true> : (void*)NS::query_kernel<false, false>); \
         }                                                                                                  \
+        static void* query_attr(bool any, bool fast) {                                                     \
+            return any ? (fast ? (void*)NS::query_attr_kernel<true, true> : (void*)NS::query_attr_kernel<true, false>) \
+                       : (fast ? (void*)NS::query_attr_kernel<false, true> : (void*)NS::query_attr_kernel<false, false>); \
+        }                                                                                                  \
         static void* batch(bool fast, bool next) {                                                         \
             return fast ? (next ? (void*)NS::first_bounce_batch_kernel<true, true> : (void*)NS::first_bounce_batch_kernel<true, false>) \
                         : (next ? (void*)NS::first_bounce_batch_kernel<false, true> : (void*)NS::first_bounce_batch_kernel<false, false>); \
@@ -1413,6 +1423,9 @@ static void* kernel_bounce(int m, bool fast) {
 }
 static void* kernel_query(int m, bool any, bool fast) {
     return m == 0 ? Kernels<0>::query(any, fast) : m == 1 ? Kernels<1>::query(any, fast) : Kernels<2>::query(any, fast);
+}
+static void* kernel_query_attr(int m, bool any, bool fast) {
+    return m == 0 ? Kernels<0>::query_attr(any, fast) : m == 1 ? Kernels<1>::query_attr(any, fast) : Kernels<2>::query_attr(any, fast);
 }
 // the timeline instantiation (rt_wave_timeline): S_ref, the fast kernels
 static void* kernel_timeline_first(bool next) {
@@ -2761,8 +2774,15 @@ static int query_check(rt_ctx* c, const char* who, const void* rays, int64_t n, 
     return RT_OK;
 }
 
-// checked arguments, n > 0
-static int query_enqueue(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32_t flags, rt_hit* d_hits, hipStream_t s) {
+// A query's record kind: rt_hit (query_kernel) or rt_hit_attr (query_attr_kernel).  Both
+// kinds share the slot, its events and its idle record, so everything that waits for a query waits for either.
+enum QueryKind { kQueryHit = 0, kQueryAttr = 1 };
+static void* kernel_query_of(QueryKind kind, int m, bool any, bool fast) {
+    return kind == kQueryAttr ? kernel_query_attr(m, any, fast) : kernel_query(m, any, fast);
+}
+
+// checked arguments, n > 0; d_hits: rt_hit[n] or rt_hit_attr[n], by kind
+static int query_enqueue(rt_ctx* c, QueryKind kind, const rt_ray* d_rays, int64_t n, uint32_t flags, void* d_hits, hipStream_t s) {
     int rc = RT_OK;
     rt_ctx::FrameSlot* Lp = nullptr;
     if ((rc = slot_for(c, (void*)s, kQueryKey, &Lp))) return rc;
@@ -2781,14 +2801,16 @@ static int query_enqueue(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32_t fl
                     (sc.fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,
                     sc.clean};
     const bool fast = S.clean != 0 && !sc.split;   // as for frames (render_frames)
-    if (!c->query_grid[math]) {
+    int& qgrid = c->query_grid[kind][math];
+    if (!qgrid) {
         int cus = 0, b1 = 0;
         HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, (const void*)kernel_query(math, false, true), 256, 0));
-        c->query_grid[math] = std::max(8, std::max(b1, 1) * cus * RTK_QUERY_GRID_PCT / 100);
+        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, (const void*)kernel_query_of(kind, math, false, true), 256, 0));
+        qgrid = std::max(8, std::max(b1, 1) * cus * RTK_QUERY_GRID_PCT / 100);
     }
     // the stack columns are sized for the mode's whole grid, whatever n is: a later, larger query allocates nothing
-    const size_t full = (size_t)c->query_grid[math];
+    // (ensure keeps a larger allocation, so the two kinds share the slot's columns)
+    const size_t full = (size_t)qgrid;
     const uint32_t ngroups = (uint32_t)((n + rtk::kSegRays - 1) / rtk::kSegRays);
     const uint32_t grid = (uint32_t)std::min<size_t>(full, (ngroups + 3u) / 4u);
     if ((rc = ensure(c, L.d_gstack, L.gstack_cap, full * rtk::kBlockThreads * rtk::kGlobalStack))) return rc;
@@ -2807,7 +2829,7 @@ static int query_enqueue(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32_t fl
     HIPC(c, hipMemsetAsync(L.d_qcnt, 0, (rtk::kCursorSet + 32) * sizeof(uint32_t), s));
     (void)hipGetLastError();
     void* args[] = {&S, &O, &Q};
-    HIPC(c, hipExtLaunchKernel(kernel_query(math, any, fast), dim3(grid), dim3(rtk::kBlockThreads), args, 0, s, L.qev[0],
+    HIPC(c, hipExtLaunchKernel(kernel_query_of(kind, math, any, fast), dim3(grid), dim3(rtk::kBlockThreads), args, 0, s, L.qev[0],
                                L.qev[1], 0));
     HIPC(c, hipGetLastError());
     HIPC(c, hipEventRecord(L.idle, s));
@@ -2816,17 +2838,22 @@ static int query_enqueue(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32_t fl
     return RT_OK;
 }
 
-int rt_trace_rays_device(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32_t flags, rt_hit* d_hits, void* stream) {
-    if (const int rc = query_check(c, "rt_trace_rays_device", d_rays, n, flags, d_hits)) return rc;
+// the two entry points of either record kind; `who` names the caller's
+static int trace_rays_device(rt_ctx* c, QueryKind kind, const char* who, const rt_ray* d_rays, int64_t n, uint32_t flags,
+                             void* d_hits, void* stream) {
+    if (const int rc = query_check(c, who, d_rays, n, flags, d_hits)) return rc;
     if (n == 0) return RT_OK;
-    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_hits & 7u))
-        return set_err(c, "rt_trace_rays_device: d_rays must be 16-byte aligned and d_hits 8-byte aligned", RT_ERR_INVALID_ARG);
+    const uintptr_t hmask = kind == kQueryAttr ? 15u : 7u;
+    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_hits & hmask))
+        return set_err(c, std::string(who) + (kind == kQueryAttr ? ": d_rays and d_hits must be 16-byte aligned"
+                                                                 : ": d_rays must be 16-byte aligned and d_hits 8-byte aligned"),
+                       RT_ERR_INVALID_ARG);
     HIPC(c, hipSetDevice(c->device));
-    return query_enqueue(c, d_rays, n, flags, d_hits, stream ? (hipStream_t)stream : c->stream);
+    return query_enqueue(c, kind, d_rays, n, flags, d_hits, stream ? (hipStream_t)stream : c->stream);
 }
 
-int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int64_t n, uint32_t flags, rt_hit* hits) {
-    if (const int rc = query_check(c, "rt_trace_rays", rays, n, flags, hits)) return rc;
+static int trace_rays_host(rt_ctx* c, QueryKind kind, const char* who, const rt_ray* rays, int64_t n, uint32_t flags, void* hits) {
+    if (const int rc = query_check(c, who, rays, n, flags, hits)) return rc;
     if (n == 0) return RT_OK;
     HIPC(c, hipSetDevice(c->device));
     // pinned host memory the device can reach (hipHostMalloc, or registered as mapped) is used
@@ -2839,8 +2866,9 @@ int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int64_t n, uint32_t flags, rt_h
         (void)hipGetLastError();   // pageable memory: not an error
         return nullptr;
     };
+    const size_t rec = kind == kQueryAttr ? sizeof(rt_hit_attr) : sizeof(rt_hit);
     const rt_ray* d_rays = (const rt_ray*)mapped(rays, 16);
-    rt_hit* d_hits = (rt_hit*)mapped(hits, 8);
+    void* d_hits = mapped(hits, kind == kQueryAttr ? 16 : 8);
     int rc = RT_OK;
     if (!d_rays) {
         if ((rc = ensure(c, c->d_qrays, c->qrays_cap, (size_t)n * 2))) return rc;
@@ -2848,14 +2876,30 @@ int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int64_t n, uint32_t flags, rt_h
         d_rays = (const rt_ray*)c->d_qrays;
     }
     const bool back = !d_hits;
-    if (back) {
-        if ((rc = ensure(c, c->d_qhits, c->qhits_cap, (size_t)n))) return rc;
-        d_hits = (rt_hit*)c->d_qhits;
+    if (back) {   // d_qhits counts 8-B words: n of them for rt_hit, 8 n for rt_hit_attr
+        if ((rc = ensure(c, c->d_qhits, c->qhits_cap, (size_t)n * (rec / sizeof(uint2))))) return rc;
+        d_hits = c->d_qhits;
     }
-    if ((rc = query_enqueue(c, d_rays, n, flags, d_hits, c->stream))) return rc;
-    if (back) HIPC(c, hipMemcpyAsync(hits, d_hits, (size_t)n * sizeof(rt_hit), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = query_enqueue(c, kind, d_rays, n, flags, d_hits, c->stream))) return rc;
+    if (back) HIPC(c, hipMemcpyAsync(hits, d_hits, (size_t)n * rec, hipMemcpyDeviceToHost, c->stream));
     HIPC(c, wait_ctx(c, c->stream));
     return RT_OK;
+}
+
+int rt_trace_rays_device(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32_t flags, rt_hit* d_hits, void* stream) {
+    return trace_rays_device(c, kQueryHit, "rt_trace_rays_device", d_rays, n, flags, d_hits, stream);
+}
+
+int rt_trace_rays(rt_ctx* c, const rt_ray* rays, int64_t n, uint32_t flags, rt_hit* hits) {
+    return trace_rays_host(c, kQueryHit, "rt_trace_rays", rays, n, flags, hits);
+}
+
+int rt_trace_rays_attr_device(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32_t flags, rt_hit_attr* d_hits, void* stream) {
+    return trace_rays_device(c, kQueryAttr, "rt_trace_rays_attr_device", d_rays, n, flags, d_hits, stream);
+}
+
+int rt_trace_rays_attr(rt_ctx* c, const rt_ray* rays, int64_t n, uint32_t flags, rt_hit_attr* hits) {
+    return trace_rays_host(c, kQueryAttr, "rt_trace_rays_attr", rays, n, flags, hits);
 }
 
 int rt_last_query_timing(rt_ctx* c, float* ms) {

@@ -76,9 +76,20 @@ class rt_hit(C.Structure):
     _fields_ = [("id", C.c_int32), ("t", C.c_float)]
 
 
-# the same two records as numpy dtypes (trace_rays' buffers)
+class rt_hit_attr(C.Structure):
+    _fields_ = [("id", C.c_int32), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float),
+                ("px", C.c_float), ("py", C.c_float), ("pz", C.c_float), ("ndotd", C.c_float),
+                ("ngx", C.c_float), ("ngy", C.c_float), ("ngz", C.c_float), ("reserved0", C.c_uint32),
+                ("nsx", C.c_float), ("nsy", C.c_float), ("nsz", C.c_float), ("reserved1", C.c_uint32)]
+
+
+# the same records as numpy dtypes (trace_rays' and trace_rays_attr's buffers)
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("reserved", np.uint32)])
 HIT_DTYPE = np.dtype([("id", np.int32), ("t", np.float32)])
+HIT_ATTR_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32),
+                           ("p", np.float32, 3), ("ndotd", np.float32),
+                           ("ng", np.float32, 3), ("reserved0", np.uint32),
+                           ("ns", np.float32, 3), ("reserved1", np.uint32)])
 
 
 class rt_mesh_view(C.Structure):
@@ -113,7 +124,8 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_refit_nodes", "rt_update_vertices", "rt_update_vertices_device", "rt_scene_bounds",
                "rt_last_update_timing", "rt_build_bvh", "rt_build_bvh_device", "rt_last_build_timing",
                "rt_build_scene", "rt_build_scene_device", "rt_last_scene_build_timing", "rt_refit_level_counts",
-               "rt_scene_sah", "rt_trace_rays", "rt_trace_rays_device", "rt_last_query_timing"]
+               "rt_scene_sah", "rt_trace_rays", "rt_trace_rays_device", "rt_last_query_timing",
+               "rt_trace_rays_attr", "rt_trace_rays_attr_device"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
                 "rt_mesh_load_dae", "rt_mesh_save_dae",
                 "rt_mesh_gen_cornell", "rt_mesh_gen_torus_knot", "rt_mesh_gen_heightfield", "rt_mesh_gen_random",
@@ -208,6 +220,8 @@ def lib() -> C.CDLL:
             "rt_scene_sah": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
             "rt_trace_rays": (C.c_int, [vp, vp, C.c_int64, u32, vp]),
             "rt_trace_rays_device": (C.c_int, [vp, vp, C.c_int64, u32, vp, vp]),
+            "rt_trace_rays_attr": (C.c_int, [vp, vp, C.c_int64, u32, vp]),
+            "rt_trace_rays_attr_device": (C.c_int, [vp, vp, C.c_int64, u32, vp, vp]),
             "rt_last_query_timing": (C.c_int, [vp, C.POINTER(f32)]),
             "rt_bvh_build_lbvh": (C.c_int, [vp, i32, C.POINTER(vp)]),
             "rt_mesh_create": (vp, []),
@@ -906,8 +920,30 @@ class Renderer:
                                           flags | (RT_FLAG_ANY_HIT if any_hit else 0), C.c_void_p(d_hits or None),
                                           C.c_void_p(stream or None)), self._h)
 
+    def trace_rays_attr(self, origins, directions, tmax=None, any_hit: bool = False, flags: int = 0) -> np.ndarray:
+        """rt_trace_rays_attr: trace_rays with a 64-byte attribute record per ray -> HIT_ATTR_DTYPE[n].
+        id and t are trace_rays' own; for a hit, u, v are the barycentrics of p1 and p2, p the frame's
+        hit point (0.001 short of the surface along the ray), ng the geometric normal by the winding,
+        ndotd = dot(ng, dir) (negative: front face) and ns the frame's shading normal, all as the
+        render path computes them in the arithmetic of `flags`.  A miss is id -1, t = the ray's tmax
+        word, everything else 0.  Arguments as trace_rays'."""
+        rays = pack_rays(origins, directions, tmax)
+        hits = np.zeros(rays.shape[0], HIT_ATTR_DTYPE)
+        _check(lib().rt_trace_rays_attr(self._h, _ptr(rays), rays.shape[0], flags | (RT_FLAG_ANY_HIT if any_hit else 0),
+                                        _ptr(hits)), self._h)
+        return hits
+
+    def trace_rays_attr_device(self, d_rays: int, n: int, d_hits: int, any_hit: bool = False, flags: int = 0,
+                               stream: Optional[int] = None) -> None:
+        """rt_trace_rays_attr_device: n rt_ray at device address d_rays -> n rt_hit_attr at d_hits (both
+        16-byte aligned), enqueued on `stream` (None = the ctx's own); returns after enqueue."""
+        _stream_arg(stream)
+        _check(lib().rt_trace_rays_attr_device(self._h, C.c_void_p(d_rays or None), n,
+                                               flags | (RT_FLAG_ANY_HIT if any_hit else 0), C.c_void_p(d_hits or None),
+                                               C.c_void_p(stream or None)), self._h)
+
     def last_query_ms(self) -> float:
-        """rt_last_query_timing: kernel time of the last trace_rays / trace_rays_device (ms)."""
+        """rt_last_query_timing: kernel time of the last ray query of either kind (ms)."""
         ms = C.c_float()
         _check(lib().rt_last_query_timing(self._h, C.byref(ms)), self._h)
         return ms.value

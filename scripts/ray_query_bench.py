@@ -11,6 +11,9 @@ one session, medians of --reps after --warmup rounds, kernel times from HIP even
   incoherent as many rays with uniform origins in the scene box, aimed at uniform points in it
 Each as ms and Mrays/s, the closest / frame ratio, and the time the query's own traffic (32 B in,
 8 B out per ray) takes at the stream-copy rate measured here.  Writes one JSON file.
+  attr_*     every buffer again through rt_trace_rays_attr_device, alternating with its
+             plain query: ms, Mrays/s and attribute / plain; its extra traffic is 56 B more out per ray
+             and 112 B more in per hit ray
 
     python scripts/ray_query_bench.py [--config c3] [--reps 20] [--warmup 5] [--flags 0] [--out profiles/ray_query/c3.json]
 """
@@ -87,11 +90,12 @@ def main():
             "any_tiled": (dev(rtamd.pack_rays(o[order], d[order])), True),
             "incoherent": (dev(rtamd.pack_rays(io, idir)), False)}
     d_hits = torch.zeros(2 * n, dtype=torch.int32, device="cuda")
+    d_attr = torch.zeros(16 * n, dtype=torch.int32, device="cuda")
     d_out = torch.zeros(n, dtype=torch.int32, device="cuda")
     d_copy = torch.zeros(40 * n, dtype=torch.uint8, device="cuda")
     d_copy2 = torch.zeros(40 * n, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
-    ms = {k: [] for k in ["frame", "copy40"] + list(bufs)}
+    ms = {k: [] for k in ["frame", "copy40"] + list(bufs) + ["attr_" + k for k in bufs]}
     hits = {}
     fflags = a.flags | rtamd.RT_FLAG_NO_SHADOW
     for it in range(a.warmup + a.reps):
@@ -100,8 +104,11 @@ def main():
         for k, (buf, any_hit) in bufs.items():
             r.trace_rays_device(buf.data_ptr(), n, d_hits.data_ptr(), any_hit=any_hit, flags=a.flags, stream=s)
             ms[k].append(r.last_query_ms())
+            r.trace_rays_attr_device(buf.data_ptr(), n, d_attr.data_ptr(), any_hit=any_hit, flags=a.flags, stream=s)
+            ms["attr_" + k].append(r.last_query_ms())
             if it == 0:
                 hits[k] = int((d_hits[0::2] >= 0).sum().item())
+                hits["attr_" + k] = int((d_attr[0::16] >= 0).sum().item())
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(stream):   # 40 B per ray read and written: twice the query's own traffic
             e0.record()
@@ -125,6 +132,11 @@ def main():
     for k in bufs:
         res[k] = {"ms": round(med[k], 4), "mrays_per_s": round(n / med[k] / 1e3, 1), "hits": hits[k],
                   "min_ms": round(min(ms[k][a.warmup:]), 4), "max_ms": round(max(ms[k][a.warmup:]), 4)}
+    for k in bufs:
+        ka = "attr_" + k
+        res[ka] = {"ms": round(med[ka], 4), "mrays_per_s": round(n / med[ka] / 1e3, 1), "hits": hits[ka],
+                   "min_ms": round(min(ms[ka][a.warmup:]), 4), "max_ms": round(max(ms[ka][a.warmup:]), 4),
+                   "over_plain": round(med[ka] / med[k], 3)}
     line = json.dumps(res)
     print(line)
     if a.out:

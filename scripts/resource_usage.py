@@ -5,6 +5,8 @@ Compiles csrc/rt_render.hip for gfx950 with -Rpass-analysis=kernel-resource-usag
 Makefile's `asm` target) and prints one line per kernel: demangled-ish name, VGPRs, AGPRs,
 SGPRs, scratch bytes per lane, LDS bytes, waves per SIMD.  Usage:
     python3 scripts/resource_usage.py [filter-substring] [-- extra make args, e.g. KDEFS=-DX=1]
+The filter is a substring of the mangled name: `query_kernel` lists the plain ray query's
+instantiations, `query_attr_kernel` the attribute query's, `query_` both.
 """
 import os
 import re
