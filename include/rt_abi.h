@@ -138,7 +138,15 @@ int rt_create(int device, rt_ctx** out);
  *   mats/nmat       arg 15 mesh_materials       Material[nmat]
  *   tri_to_mat      arg 16 tri -> material      int[nidx/3]
  * Args 3/4 (brute-force triangle list, NULL/0 in the live path) and 12
- * (debug `temp`) are dead in the reference and are not part of the ABI. */
+ * (debug `temp`) are dead in the reference and are not part of the ABI.
+ * Leaves of more than 16 references: every way a scene comes onto the device (this call,
+ * rt_build_scene, rt_scene_image_load, rt_scene_copy) derives the walk references the depth-1
+ * kernels traverse by, and a leaf reference holds at most 16.  None of the
+ * library's builders makes a larger leaf (the SBVH stops at 8, rt_build_bvh takes max_leaf 1..8);
+ * an uploaded foreign BVH that has one renders its depth-1 frames with the general traversal
+ * instead, chosen on the host as for a scene with a malformed node: the same pixels, more slowly
+ * (the 40 / 35-reference test tree: +1.2 %).  Deeper frames, the wavefront path and ray queries do not
+ * use the walk references and run as ever. */
 int rt_upload_scene(rt_ctx* ctx, const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx,
                     const rt_bvh_node* nodes, int32_t nn, const int32_t* refs, int32_t nref,
                     const rt_float4* normals, int32_t nnorm, const int32_t* normal_idx,
@@ -263,6 +271,13 @@ int rt_build_scene_device(rt_ctx* ctx, const rt_float4* d_verts, int32_t nv, con
                           const rt_material* mats /* host */, int32_t nmat, const int32_t* d_tri_to_mat, void* stream);
 int rt_last_scene_build_timing(rt_ctx* ctx, float* total_ms);
 int rt_refit_level_counts(rt_ctx* ctx, uint32_t* counts, int32_t cap, int32_t* heights);
+/* rt_scene_walk_refs (diagnostics): the walk references of the context's scene, two
+ *   words per inner record in record order, and the root's.  host_twin = 0: the array the install
+ *   derived on the device, as it stands there; *n_words = 0 and *root = 0x7FFFFFFF when the scene has
+ *   none (a leaf of more than 16 references, a malformed node, split records).  host_twin != 0: the
+ *   same from the records as they stand on the device, by the host twin of the deriving kernel.
+ *   *n_words = the array's words, of which min(cap, *n_words) are written; words may be NULL with cap 0. */
+int rt_scene_walk_refs(rt_ctx* ctx, int32_t host_twin, uint32_t* words, uint64_t cap, uint64_t* n_words, uint32_t* root);
 int rt_scene_sah(rt_ctx* ctx, double* inner_area, double* leaf_area_tris, double* root_area);
 
 /* Multi-GPU scene distribution ("ncclBroadcast of scene buffers at load").

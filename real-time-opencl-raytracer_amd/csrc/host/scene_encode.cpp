@@ -164,4 +164,27 @@ int encode_scene(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t
     return RT_OK;
 }
 
+bool derive_walk(const rt_float4* wnodes, size_t n_rec, const std::pair<int32_t, int32_t>* leaf_table, size_t n_leaf,
+                 uint32_t tri_unit, uint32_t n_refs, uint32_t root, std::vector<uint32_t>& walk, uint32_t& walk_root) {
+    static_assert(sizeof(std::pair<int32_t, int32_t>) == 8, "the escape table is {offset, count} pairs of int32");
+    std::vector<int32_t> table(2 * n_leaf);
+    for (size_t i = 0; i < n_leaf; ++i) {
+        table[2 * i] = leaf_table[i].first;
+        table[2 * i + 1] = leaf_table[i].second;
+    }
+    walk.assign(2 * n_rec, 0u);
+    bool ok = true;
+    for (size_t i = 0; i < n_rec; ++i) {
+        uint32_t r[2];
+        std::memcpy(r, &wnodes[4 * i + 3], 8);
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t w = rtrec::walk_ref(r[k], table.data(), (uint32_t)n_leaf, (uint32_t)n_rec, tri_unit, n_refs);
+            walk[2 * i + k] = w;
+            ok = ok && w != rtrec::kWalkNone;
+        }
+    }
+    walk_root = rtrec::walk_ref(root, table.data(), (uint32_t)n_leaf, (uint32_t)n_rec, tri_unit, n_refs);
+    return ok && walk_root != rtrec::kWalkNone;
+}
+
 }  // namespace rtamd

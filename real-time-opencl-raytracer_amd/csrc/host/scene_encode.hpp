@@ -31,4 +31,13 @@ int encode_scene(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t
                  const int32_t* refs, int32_t nref, const rt_float4* normals, int32_t nnorm, const int32_t* normal_idx,
                  const rt_material* mats, int32_t nmat, const int32_t* tri_to_mat, EncodedScene& out, std::string& err);
 
+// The walk references (rt_records.h) of n_rec inner records and of the root: the host twin of the kernel
+// that derives them from the records of every scene installed on the device (rt_render.hip
+// derive_walk_kernel), integer operation for integer operation.  walk gets two words per record, in
+// record order.  tri_unit: the first triangle record's offset in 16-B units (the inner records'
+// float4 count); n_refs: triangle reference records in front of the pad record.  False when a child
+// or the root has no walk reference (kWalkNone in its place): such a scene renders without the array.
+bool derive_walk(const rt_float4* wnodes, size_t n_rec, const std::pair<int32_t, int32_t>* leaf_table, size_t n_leaf,
+                 uint32_t tri_unit, uint32_t n_refs, uint32_t root, std::vector<uint32_t>& walk, uint32_t& walk_root);
+
 }  // namespace rtamd

@@ -396,9 +396,21 @@ __device__ __forceinline__ float2 rec_load2(__amdgpu_buffer_rsrc_t r, uint32_t o
     return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
 }
 
-template <bool CLOSEST, int MODE, int TR, bool SEL = false, bool GUARD = true, int OCT = -1>
+// CUR (the depth-1 kernels on a scene with walk references, DESIGN.md 7.2): `cur` is a walk reference
+// (rt_records.h) and itself the leaf cursor.  Its unit offset << 4 is the byte offset of the record the trip reads,
+// an inner record or the leaf's next triangle record, so the three record loads have no select, no
+// decode and no exec region in front of them, and tk, tend and tri_off are gone; an inner lane's two
+// child references come from the walk array, 8 B at walk_off + (cur << 1).  A leaf lane steps to its
+// next record by one add (kWalkNext: three units on, one reference fewer) and pops after the record
+// whose count field is 0.  An empty leaf is one trip on the all-zero pad record, which cannot hit by
+// arithmetic alone in any mode: e1 = e2 = 0 give det = 0, its reciprocal inf, u = 0 * inf = NaN and
+// so t = NaN, and t < th is false (tests/test_walk_cursor_gpu.py).  Every lane's visits, tests,
+// stack operations and fetches are those of the other form, but for the record an empty leaf's one
+// trip reads: the pad record here, the record its reference names (triangle record 0) there.
+template <bool CLOSEST, int MODE, int TR, bool SEL = false, bool GUARD = true, int OCT = -1, bool CUR = false>
 __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, float& tHit, const Stack& st,
                                               int& result) {
+    static_assert(!CUR || SEL, "the cursor loop is the depth-1 kernels'");
     // The trimmed trip (DESIGN.md 7.2) is the depth-1 kernels' (SEL): the uniform prologue loop and the
     // lean main-loop head (kLean: offset select next to the leaf compare, child refs loaded inside the
     // inner step's region), the slab test on scalar operands (kScalarBox 2) and the shift-add decode
@@ -415,7 +427,7 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
     // 2.5-ulp one in S_ref (after a traversal callers use only ori and dir, and the
     // general traversal recomputes slab_recip)
     const F3 inv_keep = F3{rp.yxy.x, rp.yxy.y, rp.yz.x};
-    uint32_t cur = S.root, nxt = 0;
+    uint32_t cur = CUR ? st.walk.root : S.root, nxt = 0;
     uint32_t sb = kStackBase;   // sc = 1
     int res = -1;
     float th = tHit;
@@ -428,7 +440,8 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
     // The decode's one scene field.  The depth-1 kernels (SEL) hold it in a VGPR through the loops: as
     // one of the scene's SGPRs it is spilled around them and comes back by v_readlane_b32, its whole
     // four-register tuple, on every arrival.
-    uint32_t tri_off = S.tri_off;
+    // CUR: the walk array's byte offset takes its place, the inner step's one scene field.
+    uint32_t tri_off = CUR ? st.walk.off : S.tri_off;
     if (SEL && kOctLoops) asm("" : "+v"(tri_off));
     // inner and triangle records share one allocation: buffer loads at a 32-bit byte offset
     // from one descriptor (no 64-bit address arithmetic per iteration)
@@ -450,11 +463,12 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
     const auto uniform_step = [&](uint32_t c0) __attribute__((always_inline)) {
         const int at = slot_get<GUARD>(col0, sb);
         const uint32_t popped = lds_get(at);
-        if (TR == 1) rtk::fetch_count(st.fc, false, cur, false);
+        if (TR == 1) rtk::fetch_count(st.fc, false, CUR ? cur >> 2 : cur, false);
         if (TR == 2) rtk::timeline_step(st.fc, CLOSEST ? 1 : 3);
-        csu4* rec = (csu4*)((const char*)S.wnodes + ((size_t)c0 << 6));
+        csu4* rec = (csu4*)((const char*)S.wnodes + ((size_t)c0 << (CUR ? 4 : 6)));
         const su4 u0 = rec[0], u1 = rec[1], u2 = rec[2];
-        const su2 u3 = *(csu2*)(rec + 3);
+        // CUR: the two walk references, one more scalar load (both offsets are below 2^31)
+        const su2 u3 = CUR ? *(csu2*)((const char*)S.wnodes + (size_t)(st.walk.off + (c0 << 1))) : *(csu2*)(rec + 3);
         const float4 q0 = make_float4(__uint_as_float(u0.x), __uint_as_float(u0.y), __uint_as_float(u0.z), __uint_as_float(u0.w));
         const float4 q1 = make_float4(__uint_as_float(u1.x), __uint_as_float(u1.y), __uint_as_float(u1.z), __uint_as_float(u1.w));
         const float4 q2 = make_float4(__uint_as_float(u2.x), __uint_as_float(u2.y), __uint_as_float(u2.z), __uint_as_float(u2.w));
@@ -486,7 +500,51 @@ __device__ __forceinline__ bool traverse_ifif(const DevScene& S, Ray& ray_io, fl
         }
     }
     if (TR == 2 && CLOSEST) rtk::timeline_mark(st.fc, 7);   // its wave-uniform prologue is over
-    while ((int)sb >= (int)kStackBase) {
+    while (CUR && (int)sb >= (int)kStackBase) {
+        const bool leaf = (int)cur < 0;
+        // (a bare cur << 4 would keep the count field's lowest bit, bit 27, as bit 31 of the offset)
+        const uint32_t off = (cur & rtrec::kWalkUnitMask) << 4;
+        const int at = slot_get<GUARD>(col0, sb);
+        const uint32_t popped = lds_get(at);
+        // (counting key of an empty leaf's trip: the other form reads, and keys, the record its reference
+        // names, triangle record 0 in every encoding of this library (scene_encode.cpp writes an empty
+        // leaf with offset 0), where this one reads the pad record, 48 B below the walk array)
+        if (TR == 1) rtk::fetch_count(st.fc, leaf, leaf ? (0x80000000u | (off == tri_off - 48u ? S.tri_off : off)) : cur >> 2);
+        if (TR == 2) rtk::timeline_step(st.fc, CLOSEST ? 0 : 2);
+        uint32_t t_issue = 0;
+        if (TR == 2 && RTK_TL_SPLIT) t_issue = (uint32_t)__builtin_amdgcn_s_memrealtime();
+        const float4 q0 = rec_load4(recs, off), q1 = rec_load4(recs, off + 16u), q2 = rec_load4(recs, off + 32u);
+        // the child refs: as below, the first instruction of the inner step's region (the timeline's
+        // split diagnostic: right after the boxes)
+        constexpr bool kRefsEarly = TR == 2 && RTK_TL_SPLIT;
+        float2 q3;
+        if (kRefsEarly) {
+            q3 = make_float2(0.0f, 0.0f);
+            if (!leaf) q3 = rec_load2(recs, tri_off + (cur << 1));
+            asm volatile("" ::: "memory");
+            asm volatile("" ::"v"(q0.x), "v"(q1.x), "v"(q2.x), "v"(q3.x));
+            rtk::timeline_wait(st.fc, CLOSEST ? 0 : 1, (uint32_t)__builtin_amdgcn_s_memrealtime() - t_issue);
+        }
+        if (!leaf) {
+            if (!kRefsEarly) {
+                q3 = rec_load2(recs, tri_off + (cur << 1));
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            inner_step<MODE, OCT>(q0, q1, q2, q3, rp, th, popped, slot_put<GUARD>(at, col0, sb), cur, nxt, sb);
+        } else {
+            const F3 e2 = F3{q2.x, q2.y, q2.z};
+            const float t = ray_tri(ray_of(rp, inv_keep), F3{q0.x, q0.y, q0.z}, F3{q1.x, q1.y, q1.z}, e2);
+            const bool hit = t < th && t > kTmin;
+            th = hit ? t : th;
+            res = hit ? __float_as_int(q0.w) : res;
+            const bool pop = cur < rtrec::kWalkLastBelow;   // count field 0: this was the leaf's last record
+            cur = pop ? nxt : cur + rtrec::kWalkNext;
+            nxt = pop ? popped : nxt;
+            sb -= pop ? 256u : 0u;
+            if (!CLOSEST) sb = hit ? kStackDone : sb;   // any-hit: first hit returns (:986)
+        }
+    }
+    while (!CUR && (int)sb >= (int)kStackBase) {
         const bool leaf = (cur & kLeafBit) != 0;
         // SEL (the depth-1 kernel): a select between the two byte offsets, so the loads issue
         // without an exec-masked branch in front of them (C3 -1.4 %, C4 -1.6 %; the wavefront
@@ -588,18 +646,21 @@ __device__ __forceinline__ void variant_count(const Stack& st, int which) {
     if (TR == 1 && (uint32_t)(threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_read_exec()))
         atomicAdd(st.vc + (CLOSEST ? 0 : 9) + which, 1ull);
 }
-template <bool CLOSEST, int TR, bool SEL = false, bool GUARD = true, bool OCTS = false>
+// WALK: the traversal runs the cursor loop (traverse_ifif's CUR): the depth-1 kernels launched for a
+// scene with walk references.  The host picks those instantiations, product, counting and timeline
+// alike; a scene without walk references gets the ones without WALK.
+template <bool CLOSEST, int TR, bool SEL = false, bool GUARD = true, bool OCTS = false, bool WALK = false>
 __device__ __forceinline__ bool traverse_fast(const DevScene& S, Ray& ray, float& tHit, const Stack& st,
                                               int& result) {
     if (!S.fast_div || __builtin_amdgcn_ballot_w64(!fast_div_ok(ray))) {
         variant_count<CLOSEST, TR>(st, 0);
-        return traverse_ifif<CLOSEST, 2, TR, SEL, GUARD>(S, ray, tHit, st, result);
+        return traverse_ifif<CLOSEST, 2, TR, SEL, GUARD, -1, WALK>(S, ray, tHit, st, result);
     }
     if (kMath != 2) {
         const bool z = ray.dir.x == 0.0f || ray.dir.y == 0.0f || ray.dir.z == 0.0f;
         if (__builtin_amdgcn_ballot_w64(z)) {
             variant_count<CLOSEST, TR>(st, 0);
-            return traverse_ifif<CLOSEST, 1, TR, SEL, GUARD>(S, ray, tHit, st, result);
+            return traverse_ifif<CLOSEST, 1, TR, SEL, GUARD, -1, WALK>(S, ray, tHit, st, result);
         }
     }
     if (OCTS) {
@@ -614,31 +675,31 @@ __device__ __forceinline__ bool traverse_fast(const DevScene& S, Ray& ray, float
         if (__builtin_amdgcn_ballot_w64(z) == 0 && uniform) {
             variant_count<CLOSEST, TR>(st, 1 + oct);
             switch (oct) {
-                case 0: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 0>(S, ray, tHit, st, result);
-                case 1: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 1>(S, ray, tHit, st, result);
-                case 2: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 2>(S, ray, tHit, st, result);
-                case 3: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 3>(S, ray, tHit, st, result);
-                case 4: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 4>(S, ray, tHit, st, result);
-                case 5: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 5>(S, ray, tHit, st, result);
-                case 6: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 6>(S, ray, tHit, st, result);
-                default: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 7>(S, ray, tHit, st, result);
+                case 0: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 0, WALK>(S, ray, tHit, st, result);
+                case 1: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 1, WALK>(S, ray, tHit, st, result);
+                case 2: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 2, WALK>(S, ray, tHit, st, result);
+                case 3: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 3, WALK>(S, ray, tHit, st, result);
+                case 4: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 4, WALK>(S, ray, tHit, st, result);
+                case 5: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 5, WALK>(S, ray, tHit, st, result);
+                case 6: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 6, WALK>(S, ray, tHit, st, result);
+                default: return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, 7, WALK>(S, ray, tHit, st, result);
             }
         }
     }
     variant_count<CLOSEST, TR>(st, 0);
-    return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD>(S, ray, tHit, st, result);
+    return traverse_ifif<CLOSEST, 0, TR, SEL, GUARD, -1, WALK>(S, ray, tHit, st, result);
 }
 
 // Closest-hit / any-hit of one ray: the fast traversal, restarted with the general
 // code when its stack outgrows the LDS part (counted in O.restarts).  t_restart: what t was on
 // entry, which the restart begins from again (a frame's rays: HitRecordInit's constant; a query's
 // ray: its own tmax).
-template <bool CLOSEST, bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true, bool OCTS = false>
+template <bool CLOSEST, bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true, bool OCTS = false, bool WALK = false>
 __device__ __forceinline__ int trace(const DevScene& S, const Outputs& O, Ray& ray, float& t, const Stack& st,
                                      bool& overflow, float t_restart = 4294967296.0f) {
     int hit;
     if (FASTONLY) {
-        if (traverse_fast<CLOSEST, TR, SEL, GUARD, OCTS>(S, ray, t, st, hit)) return hit;
+        if (traverse_fast<CLOSEST, TR, SEL, GUARD, OCTS, WALK>(S, ray, t, st, hit)) return hit;
         atomicAdd(O.restarts, 1u);
         t = t_restart;
     }
@@ -702,12 +763,12 @@ __device__ __forceinline__ void park_next(const F3& dir, const F3& normal, const
 }
 
 // Shadow ray from a hit (volumeRender.cl:1437-1460): any-hit, shadowed iff hit && t > 0.025.
-template <bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true, bool OCTS = false>
+template <bool FASTONLY, int TR = 0, bool SEL = false, bool GUARD = true, bool OCTS = false, bool WALK = false>
 __device__ __forceinline__ float shadow_coef(const DevScene& S, const Outputs& O, const F3& hitpoint, const F3& L,
                                              const Stack& st, bool& overflow, int& sh) {
     Ray sray = ray_init(mad3(L, 0.001f, hitpoint), L);   // hitpoint + L * 0.001f
     float ts = 4294967296.0f;
-    sh = trace<false, FASTONLY, TR, SEL, GUARD, OCTS>(S, O, sray, ts, st, overflow);
+    sh = trace<false, FASTONLY, TR, SEL, GUARD, OCTS, WALK>(S, O, sray, ts, st, overflow);
     return (sh >= 0 && ts > 0.025f) ? 0.25f : 1.0f;
 }
 
@@ -824,13 +885,13 @@ enum { kFinishMiss = 0, kFinishHit = 1, kContinue = 2 };
 // only the shadow sum is stored after the shadow trace, so nothing is parked across that
 // trace (no LDS for the next ray).  `color += rez` before the shadow trace is the same
 // float op on the same operands as after it (volumeRender.cl:1483).
-template <bool FASTONLY, int TR = 0, bool SEL = false, bool OCTS = false>
+template <bool FASTONLY, int TR = 0, bool SEL = false, bool OCTS = false, bool WALK = false>
 __device__ __forceinline__ int wf_bounce(const DevScene& S, const Frame& F, const Outputs& O, const WQ& W,
                                          int want_aux, uint32_t pix, int k, Ray ray, F3& color, float& ss,
                                          const Stack& st, bool& overflow) {
     const int depth = F.depth;
     float tHit = 4294967296.0f;
-    const int hit = trace<true, FASTONLY, TR, SEL, true, OCTS>(S, O, ray, tHit, st, overflow);
+    const int hit = trace<true, FASTONLY, TR, SEL, true, OCTS, WALK>(S, O, ray, tHit, st, overflow);
     if (TR == 2) rtk::timeline_mark(st.fc, 4);   // the closest-hit traversal is done
     if (want_aux) {
         O.hits[((size_t)pix * depth + k) * 2] = hit;
@@ -856,7 +917,7 @@ __device__ __forceinline__ int wf_bounce(const DevScene& S, const Frame& F, cons
     float coef = 1.0f;
     if (!(F.flags & RT_FLAG_NO_SHADOW)) {
         int sh;
-        coef = shadow_coef<FASTONLY, TR, SEL, true, OCTS>(S, O, hitpoint, L, st, overflow, sh);
+        coef = shadow_coef<FASTONLY, TR, SEL, true, OCTS, WALK>(S, O, hitpoint, L, st, overflow, sh);
         if (want_aux) O.hits[((size_t)pix * depth + k) * 2 + 1] = sh;
     }
     ss += coef;
@@ -888,10 +949,10 @@ __device__ __forceinline__ void wf_aux_init(const Outputs& O, int depth, uint32_
 // depth-1 kernel): with O.frame_rows the packed pixel goes to its place in the whole frame.
 // qbase: added to the pixel index a continuing ray carries in the queue (the frame's first
 // pixel in a batch launch's pixel space, first_bounce_batch_kernel; 0 otherwise).
-template <bool FASTONLY, int TR, bool SEL, bool ROWS>
+template <bool FASTONLY, int TR, bool SEL, bool ROWS, bool WALK>
 __device__ __forceinline__ void first_bounce_pixel(const DevScene& S, const Frame& F, const Outputs& O, const WQ& W,
                                                    int want_aux, uint32_t x, uint32_t lr, uint32_t* lds, uint32_t* fc,
-                                                   uint32_t qbase = 0u) {
+                                                   rtk::Walk walk, uint32_t qbase = 0u) {
     const uint32_t y = lr < F.local_rows ? rtk::frame_row(F, lr) : F.h;
     const bool valid = x < F.w && y < F.h;
     const uint32_t pix = valid ? lr * F.w + x : 0u;
@@ -910,8 +971,9 @@ __device__ __forceinline__ void first_bounce_pixel(const DevScene& S, const Fram
             st.glb = O.gstack + pix;
             st.gstride = O.local_pixels;
             st.fc = fc;
+            if (WALK) st.walk = walk;
             if (TR == 1) st.vc = O.fcount + rtk::kFetchCounts;
-            const int r = wf_bounce<FASTONLY, TR, SEL, kOctLoops && SEL>(S, F, O, W, want_aux, pix + qbase, 0, ray, color, ss, st, overflow);
+            const int r = wf_bounce<FASTONLY, TR, SEL, kOctLoops && SEL, WALK>(S, F, O, W, want_aux, pix + qbase, 0, ray, color, ss, st, overflow);
             if (r != kContinue) wf_finish(O, want_aux, pix, oi, color, ss, r == kFinishHit ? 1 : 0);
         }
     }
@@ -928,8 +990,8 @@ __device__ __forceinline__ void first_bounce_pixel(const DevScene& S, const Fram
 // diagnostic instantiation (rt_wave_timeline) that stamps every wave's start, end of its
 // pixels and end of the block epilogue and counts its loop trips (rtk::timeline_*), at the
 // product kernel's wave bound.
-template <bool FASTONLY, bool NEXT, int TR = 0>
-__global__ void __launch_bounds__(256, TR == 1 ? 4 : kMath != 2 ? RTK_WF_WAVES : NEXT ? RTK_FBN_REF_WAVES : RTK_FB_WAVES) first_bounce_kernel(DevScene S, Frame F, Outputs O, WQ W, int want_aux) {
+template <bool FASTONLY, bool NEXT, int TR = 0, bool WALK = !NEXT>
+__global__ void __launch_bounds__(256, TR == 1 ? 4 : kMath != 2 ? RTK_WF_WAVES : NEXT ? RTK_FBN_REF_WAVES : RTK_FB_WAVES) first_bounce_kernel(DevScene S, Frame F, Outputs O, WQ W, int want_aux, rtk::Walk walk) {
     __shared__ uint32_t s_stack[4][rtk::kLdsRows][64];
     __shared__ uint32_t s_fc[TR == 1 ? 8 * 256 : TR == 2 ? 4 * rtk::kTlWords : 1];
     const int lane = threadIdx.x & 63;
@@ -949,8 +1011,9 @@ __global__ void __launch_bounds__(256, TR == 1 ? 4 : kMath != 2 ? RTK_WF_WAVES :
     if (!NEXT) Wn.out = nullptr;   // depth 1: nothing continues
     Wn.seg = tb * 4u + (uint32_t)wave;
     Wn.seg_fill = &s_fill[wave];
-    first_bounce_pixel<FASTONLY, TR, !NEXT, !NEXT>(S, F, O, Wn, want_aux, x, lr, lds,
-                                                                  TR == 1 ? &s_fc[threadIdx.x] : TR == 2 ? &s_fc[wave * rtk::kTlWords] : nullptr);
+    static_assert(!WALK || !NEXT, "the cursor loop is the depth-1 kernels'");
+    first_bounce_pixel<FASTONLY, TR, !NEXT, !NEXT, WALK>(S, F, O, Wn, want_aux, x, lr, lds,
+                                                                  TR == 1 ? &s_fc[threadIdx.x] : TR == 2 ? &s_fc[wave * rtk::kTlWords] : nullptr, walk);
     if (NEXT) rtk::seg_close(Wn, Wn.seg);
     if (TR == 1) rtk::fetch_count_flush(s_fc, O.fcount);
     const uint32_t t_pix = TR == 2 ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
@@ -973,7 +1036,7 @@ __global__ void __launch_bounds__(256, TR == 1 ? 4 : kMath != 2 ? RTK_WF_WAVES :
 // pixel of its own frame (at depth > 1 frame_px is the frames' stride, so that pixel is out[f * stride + p]).
 // Per pixel this is first_bounce_kernel's code, so every frame equals its own single render.
 template <bool FASTONLY, bool NEXT>
-__global__ void __launch_bounds__(256, kMath != 2 ? RTK_WF_WAVES : NEXT ? RTK_FBN_REF_WAVES : RTK_FB_WAVES) first_bounce_batch_kernel(DevScene S, Frame F, Outputs O, WQ W, rtk::BatchCams C) {
+__global__ void __launch_bounds__(256, kMath != 2 ? RTK_WF_WAVES : NEXT ? RTK_FBN_REF_WAVES : RTK_FB_WAVES) first_bounce_batch_kernel(DevScene S, Frame F, Outputs O, WQ W, rtk::BatchCams C, rtk::Walk walk) {
     __shared__ uint32_t s_stack[4][rtk::kLdsRows][64];
     __shared__ uint32_t s_fill[4];
     const int lane = threadIdx.x & 63;
@@ -1003,8 +1066,8 @@ __global__ void __launch_bounds__(256, kMath != 2 ? RTK_WF_WAVES : NEXT ? RTK_FB
     const uint32_t qe = RTK_XFRAME ? tb * (gridDim.x / F.num_blocks) + f : e;
     Wn.seg = qe * 4u + (uint32_t)wave;
     Wn.seg_fill = &s_fill[wave];
-    first_bounce_pixel<FASTONLY, 0, !NEXT, !NEXT>(S, Ff, Of, Wn, 0, x, lr, &s_stack[wave][rtk::kLdsGuard][lane], nullptr,
-                                                       f * C.frame_px);
+    first_bounce_pixel<FASTONLY, 0, !NEXT, !NEXT, !NEXT>(S, Ff, Of, Wn, 0, x, lr, &s_stack[wave][rtk::kLdsGuard][lane], nullptr,
+                                                       walk, f * C.frame_px);
     if (NEXT) rtk::seg_close(Wn, Wn.seg);
     tile_epilogue(F, e, t_start, &s_stack[0][0][0]);
 }

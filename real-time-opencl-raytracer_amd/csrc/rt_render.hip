@@ -298,11 +298,20 @@ __device__ __forceinline__ void leaf_bytes(const DevScene& S, uint32_t tri_off, 
     asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(tend) : "v"(c3), "v"(tk));
 }
 
+// The walk references of the installed scene (rt_records.h), a trailing argument of the
+// first-bounce kernels: the root's walk reference and the array's byte offset in the record
+// allocation.  Only the depth-1 kernels read it (the host launches them only when off != 0); it is no
+// part of DevScene so that every other kernel's arguments, and so its code, stay as they are.
+struct Walk {
+    uint32_t root, off;
+};
+
 struct Stack {
     uint32_t* lds;      // this lane's column: lds[i * 64], i >= -kLdsGuard
     uint32_t* glb;      // this pixel's column: glb[(i - kLdsStack) * gstride]
     uint64_t gstride;
     uint32_t* fc = nullptr;       // measurement instantiation: this lane's 8 fetch counters (LDS, stride 256)
+    Walk walk{};                  // the depth-1 kernels' walk references (traverse_ifif with SEL); unused elsewhere
     unsigned long long* vc = nullptr;   // measurement instantiation: the frame's 18 loop-variant counters (traverse_fast)
     __device__ __forceinline__ uint32_t get(int i) const {
         return i < kLdsStack ? lds[i * 64] : glb[(uint64_t)(i - kLdsStack) * gstride];
@@ -988,6 +997,34 @@ __global__ void __launch_bounds__(256) frame_checksum_kernel(const uint32_t* __r
 #undef RTK_NS
 #undef RTK_MATH
 
+// The walk references of a scene's inner records (rt_records.h), derived from the records just placed
+// on the device: one thread per inner record, its two child references; thread 0 also the root's.
+// status[0] != 0 afterwards: some reference has no walk form, the scene renders without the array;
+// status[1]: the root's walk reference.  The host twin is rtamd::derive_walk (csrc/host/scene_encode.cpp).
+namespace rtk {
+__global__ void __launch_bounds__(256) derive_walk_kernel(const float4* __restrict__ wnodes, uint32_t n_rec,
+                                                          const int2* __restrict__ leaf_table, uint32_t n_leaf, uint32_t tri_unit,
+                                                          uint32_t n_refs, uint32_t root, uint2* __restrict__ walk,
+                                                          uint32_t* __restrict__ status) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const int32_t* table = reinterpret_cast<const int32_t*>(leaf_table);
+    bool bad = false;
+    if (i < n_rec) {
+        const float4 q3 = wnodes[(size_t)i * 4 + 3];
+        const uint32_t w0 = rtrec::walk_ref(__float_as_uint(q3.x), table, n_leaf, n_rec, tri_unit, n_refs);
+        const uint32_t w1 = rtrec::walk_ref(__float_as_uint(q3.y), table, n_leaf, n_rec, tri_unit, n_refs);
+        walk[i] = make_uint2(w0, w1);
+        bad = w0 == rtrec::kWalkNone || w1 == rtrec::kWalkNone;
+    }
+    if (i == 0) {
+        const uint32_t wr = rtrec::walk_ref(root, table, n_leaf, n_rec, tri_unit, n_refs);
+        status[1] = wr;
+        bad = bad || wr == rtrec::kWalkNone;
+    }
+    if (bad) atomicOr(status, 1u);
+}
+}  // namespace rtk
+
 // ============================================================================
 // Host side: context, upload/repack, launch.
 // ============================================================================
@@ -1009,6 +1046,14 @@ struct Scene {
     uint32_t root = 0, n_inner = 0;
     int fast_div = 0, clean = 0;
     bool split = false;           // records >= 2 GiB: two allocations (kRec, kTris), general traversal only
+    // Walk references (rt_records.h), derived by install_scene from the records and no part of the scene
+    // image: after the triangle records in kRec come two zero units (with the pad float4 that ends the
+    // triangle records, one all-zero 48-B record), the array (8 B per inner record) and one status unit.
+    // walk_off: the array's byte offset in kRec, 0: none (split records, or a reference without a walk form)
+    uint32_t walk_root = 0, walk_off = 0;
+    static size_t walk_units(size_t n_wnodes4) { return 2 + (n_wnodes4 / 4 + 1) / 2 + 1; }
+    size_t walk_unit0() const { return n_wnodes4 + n_tris4 + 2; }   // the array's first 16-B unit
+    size_t rec_units() const { return n_wnodes4 + n_tris4 + (split ? 0 : walk_units(n_wnodes4)); }
     bool have_bounds = false;     // rt_scene_bounds: the uploaded / built / refit root box
     rt_float4 bounds_min{}, bounds_max{};
     // Animated geometry (rt_update_vertices): a refittable scene keeps per-triangle vertex / normal
@@ -1267,7 +1312,9 @@ static uint64_t record_limit() {
     return lim && lim < 0x80000000ull ? lim : 0x80000000ull;
 }
 
-static bool records_split(size_t n_wnodes4, size_t n_tris4) { return (n_wnodes4 + n_tris4) * 16 >= record_limit(); }
+static bool records_split(size_t n_wnodes4, size_t n_tris4) {
+    return (n_wnodes4 + n_tris4 + Scene::walk_units(n_wnodes4)) * 16 >= record_limit();
+}
 
 // One array of a scene: from the pool where its allocation of that kind is large enough, else fresh.
 static hipError_t scene_alloc(Scene& s, int k, size_t bytes, Scene::Owned* pool) {
@@ -1288,7 +1335,7 @@ static hipError_t scene_alloc_records(Scene& s, size_t n_wnodes4, size_t n_tris4
                                       Scene::Owned* pool) {
     s.n_wnodes4 = n_wnodes4; s.n_tris4 = n_tris4; s.n_shade4 = n_shade4; s.n_leaf = n_leaf;
     s.split = records_split(n_wnodes4, n_tris4);
-    hipError_t e = scene_alloc(s, Scene::kRec, (s.split ? n_wnodes4 : n_wnodes4 + n_tris4) * sizeof(float4), pool);
+    hipError_t e = scene_alloc(s, Scene::kRec, (s.split ? n_wnodes4 : s.rec_units()) * sizeof(float4), pool);
     if (e == hipSuccess && s.split) e = scene_alloc(s, Scene::kTris, n_tris4 * sizeof(float4), pool);
     if (e == hipSuccess) e = scene_alloc(s, Scene::kShade, n_shade4 * sizeof(float4), pool);
     return e == hipSuccess ? scene_alloc(s, Scene::kLeaf, n_leaf * sizeof(int2), pool) : e;
@@ -1328,8 +1375,37 @@ static int drop_scene(rt_ctx* c) {
     return RT_OK;
 }
 
+// The walk references of a scene whose records are in place (every producer has waited for its copies
+// and kernels): zero the units after the triangle records, derive the array, read the status back.
+static int derive_walk(rt_ctx* c, Scene& s) {
+    s.walk_root = s.walk_off = 0;
+    if (s.split || !s.wnodes() || s.n_tris4 == 0) return RT_OK;
+    // RTAMD_NO_WALK=1 (tests): the scene is installed without walk references, as one with a leaf of
+    // more than 16 references is, so that the two loop forms can be compared on one scene
+    if (const char* v = std::getenv("RTAMD_NO_WALK"); v && v[0] == '1') return RT_OK;
+    HIPC(c, hipSetDevice(c->device));
+    const uint32_t n_rec = (uint32_t)(s.n_wnodes4 / 4);
+    float4* w0 = s.wnodes() + s.n_wnodes4 + s.n_tris4;
+    HIPC(c, hipMemsetAsync(w0, 0, Scene::walk_units(s.n_wnodes4) * sizeof(float4), c->stream));
+    uint2* walk = (uint2*)(s.wnodes() + s.walk_unit0());
+    uint32_t* status = (uint32_t*)(w0 + Scene::walk_units(s.n_wnodes4) - 1);
+    hipLaunchKernelGGL(rtk::derive_walk_kernel, dim3((std::max(n_rec, 1u) + 255u) / 256u), dim3(256), 0, c->stream,
+                       (const float4*)s.wnodes(), n_rec, (const int2*)s.leaf(), (uint32_t)s.n_leaf, (uint32_t)s.n_wnodes4,
+                       (uint32_t)((s.n_tris4 - 1) / 3), s.root, walk, status);
+    HIPC(c, hipGetLastError());
+    uint32_t st[2] = {1u, 0u};
+    HIPC(c, hipMemcpyAsync(st, status, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (st[0] == 0) {
+        s.walk_root = st[1];
+        s.walk_off = (uint32_t)(s.walk_unit0() * 16);
+    }
+    return RT_OK;
+}
+
 // The single place that replaces the context's scene.
 static int install_scene(rt_ctx* c, Scene&& s) {
+    if (const int rc = derive_walk(c, s)) return rc;
     if (const int rc = drop_scene(c)) return rc;
     c->scene = std::move(s);
     c->have_scene = true;
@@ -1381,8 +1457,10 @@ template <int M> struct Kernels;
         static void* bounce(bool fast) {                                                                   \
             return fast ? (void*)NS::wf_bounce_kernel<true> : (void*)NS::wf_bounce_kernel<false>;          \
         }                                                                                                  \
-        static void* traced(bool next) {                                                                   \
-            return next ? (void*)NS::first_bounce_kernel<true, true, 1> : (void*)NS::first_bounce_kernel<true, false, 1>; \
+        static void* traced(bool next, bool walk) {                                                        \
+            return next ? (void*)NS::first_bounce_kernel<true, true, 1>                                    \
+                        : walk ? (void*)NS::first_bounce_kernel<true, false, 1, true>                      \
+                               : (void*)NS::first_bounce_kernel<true, false, 1, false>;                    \
         }                                                                                                  \
         static void* traced_bounce() { return (void*)NS::wf_bounce_kernel<true, 1>; }                     \
         static void* query(bool any, bool fast) {                                                          \
@@ -1412,8 +1490,8 @@ static void* kernel_batch(int m, bool fast, bool next) {
 static void* kernel_fused(int m, bool fast) {
     return m == 0 ? Kernels<0>::fused(fast) : m == 1 ? Kernels<1>::fused(fast) : Kernels<2>::fused(fast);
 }
-static void* kernel_traced(int m, bool next) {
-    return m == 0 ? Kernels<0>::traced(next) : m == 1 ? Kernels<1>::traced(next) : Kernels<2>::traced(next);
+static void* kernel_traced(int m, bool next, bool walk) {
+    return m == 0 ? Kernels<0>::traced(next, walk) : m == 1 ? Kernels<1>::traced(next, walk) : Kernels<2>::traced(next, walk);
 }
 static void* kernel_traced_bounce(int m) {
     return m == 0 ? Kernels<0>::traced_bounce() : m == 1 ? Kernels<1>::traced_bounce() : Kernels<2>::traced_bounce();
@@ -1428,8 +1506,9 @@ static void* kernel_query_attr(int m, bool any, bool fast) {
     return m == 0 ? Kernels<0>::query_attr(any, fast) : m == 1 ? Kernels<1>::query_attr(any, fast) : Kernels<2>::query_attr(any, fast);
 }
 // the timeline instantiation (rt_wave_timeline): S_ref, the fast kernels
-static void* kernel_timeline_first(bool next) {
-    return next ? (void*)rtk_ref::first_bounce_kernel<true, true, 2> : (void*)rtk_ref::first_bounce_kernel<true, false, 2>;
+static void* kernel_timeline_first(bool next, bool walk) {
+    return next ? (void*)rtk_ref::first_bounce_kernel<true, true, 2>
+                : walk ? (void*)rtk_ref::first_bounce_kernel<true, false, 2, true> : (void*)rtk_ref::first_bounce_kernel<true, false, 2, false>;
 }
 static void* kernel_timeline_bounce() { return (void*)rtk_ref::wf_bounce_kernel<true, 2>; }
 
@@ -2061,6 +2140,37 @@ int rt_last_scene_build_timing(rt_ctx* c, float* total_ms) {
     return RT_OK;
 }
 
+int rt_scene_walk_refs(rt_ctx* c, int32_t host_twin, uint32_t* words, uint64_t cap, uint64_t* n_words, uint32_t* root) {
+    if (!c || !n_words || !root || (!words && cap)) return set_err(c, "rt_scene_walk_refs: invalid argument", RT_ERR_INVALID_ARG);
+    if (!c->have_scene) return set_err(c, "rt_scene_walk_refs: no scene", RT_ERR_NO_SCENE);
+    HIPC(c, hipSetDevice(c->device));
+    const Scene& S = c->scene;
+    *n_words = 0;
+    *root = rtrec::kWalkNone;
+    const size_t n_rec = S.n_wnodes4 / 4;
+    std::vector<uint32_t> walk;
+    if (host_twin) {   // the records as they stand on the device, through rtamd::derive_walk
+        if (S.split || S.n_tris4 == 0) return RT_OK;
+        std::vector<rt_float4> wn(S.n_wnodes4);
+        std::vector<std::pair<int32_t, int32_t>> table(S.n_leaf);
+        HIPC(c, hipMemcpy(wn.data(), S.wnodes(), S.n_wnodes4 * sizeof(float4), hipMemcpyDeviceToHost));
+        if (S.n_leaf) HIPC(c, hipMemcpy(table.data(), S.leaf(), S.n_leaf * sizeof(int2), hipMemcpyDeviceToHost));
+        uint32_t wr = rtrec::kWalkNone;
+        if (!rtamd::derive_walk(wn.data(), n_rec, table.data(), table.size(), (uint32_t)S.n_wnodes4,
+                                (uint32_t)((S.n_tris4 - 1) / 3), S.root, walk, wr))
+            return RT_OK;
+        *root = wr;
+    } else {
+        if (!S.walk_off) return RT_OK;
+        walk.resize(2 * n_rec);
+        HIPC(c, hipMemcpy(walk.data(), (const char*)S.wnodes() + S.walk_off, walk.size() * 4, hipMemcpyDeviceToHost));
+        *root = S.walk_root;
+    }
+    *n_words = walk.size();
+    if (walk.size() && words) std::memcpy(words, walk.data(), std::min<uint64_t>(cap, walk.size()) * 4);
+    return RT_OK;
+}
+
 int rt_refit_level_counts(rt_ctx* c, uint32_t* counts, int32_t cap, int32_t* heights) {
     if (!c || !heights || cap < 0 || (cap > 0 && !counts))
         return set_err(c, "rt_refit_level_counts: invalid argument", RT_ERR_INVALID_ARG);
@@ -2305,7 +2415,7 @@ static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint3
                     sc.shade(),
                     sc.leaf(),
                     (uint32_t)(sc.n_wnodes4 * 16),
-                    (uint32_t)((sc.n_wnodes4 + sc.n_tris4) * 16),
+                    (uint32_t)(sc.rec_units() * 16),
                     sc.root,
                     sc.n_inner,
                     (sc.fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,
@@ -2426,6 +2536,11 @@ static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint3
     // the fast kernels (any quotient domain: traverse_fast picks the variant) need a clean scene
     // whose records one buffer descriptor covers
     const bool fast = S.clean != 0 && !sc.split;
+    // The depth-1 kernels walk by the scene's walk references.  A scene without them (a leaf of more
+    // than 16 references: only an uploaded foreign BVH has one) renders its depth-1 frames with the
+    // general traversal, as an unclean scene does: same pixels.
+    const bool fast0 = fast && (depth > 1 || sc.walk_off != 0);
+    rtk::Walk walk{sc.walk_root, sc.walk_off};
     const dim3 grid(F.num_blocks * K), block(rtk::kBlockThreads);
     int ax = aux ? 1 : 0;
     // A frame of one launch (depth 1, or the fused kernel) with RTK_EXT_EVENTS takes its timing
@@ -2474,14 +2589,14 @@ static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint3
             W.chunk_sum = sums(1);
             W.super_sum = sums(1) + nchunk;
             W.bounce = 0;
-            void* args[] = {&S, &F, &O, &W, &ax};
+            void* args[] = {&S, &F, &O, &W, &ax, &walk};
             if (traced) {   // rt_fetch_counts: the counting instantiation of the same kernel
                 O.fcount = c->trace.d_counts;
-                HIPC(c, hipLaunchKernel(kernel_traced(math, depth > 1), grid, block, args, 0, s));
+                HIPC(c, hipLaunchKernel(kernel_traced(math, depth > 1, sc.walk_off != 0), grid, block, args, 0, s));
             } else if (tline) {   // rt_wave_timeline: the stamping instantiation
                 if (!(O.wtime = tline_region(F.num_blocks * 4u)))
                     return set_err(c, "rt_wave_timeline: buffer too small", RT_ERR_INVALID_ARG);
-                HIPC(c, hipLaunchKernel(kernel_timeline_first(depth > 1), grid, block, args, 0, s));
+                HIPC(c, hipLaunchKernel(kernel_timeline_first(depth > 1, sc.walk_off != 0), grid, block, args, 0, s));
             } else if (batch) {
                 rtk::BatchCams C{};
                 for (uint32_t i = 0; i < K; ++i) {
@@ -2493,14 +2608,14 @@ static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint3
                 }
                 C.stride = bstride;
                 C.frame_px = (uint32_t)fpx;
-                void* bargs[] = {&S, &F, &O, &W, &C};
-                void* kb = kernel_batch(math, fast, depth > 1);
+                void* bargs[] = {&S, &F, &O, &W, &C, &walk};
+                void* kb = kernel_batch(math, fast0, depth > 1);
                 if (ext_ev) HIPC(c, hipExtLaunchKernel(kb, grid, block, bargs, 0, s, E.e[0], E.e[1], 0));
                 else HIPC(c, hipLaunchKernel(kb, grid, block, bargs, 0, s));
             } else if (ext_ev) {
-                HIPC(c, hipExtLaunchKernel(kernel_first(math, fast, depth > 1), grid, block, args, 0, s, E.e[0], E.e[1], 0));
+                HIPC(c, hipExtLaunchKernel(kernel_first(math, fast0, depth > 1), grid, block, args, 0, s, E.e[0], E.e[1], 0));
             } else {
-                HIPC(c, hipLaunchKernel(kernel_first(math, fast, depth > 1), grid, block, args, 0, s));
+                HIPC(c, hipLaunchKernel(kernel_first(math, fast0, depth > 1), grid, block, args, 0, s));
             }
             ++L.nframe;
         }
@@ -2795,7 +2910,7 @@ static int query_enqueue(rt_ctx* c, QueryKind kind, const rt_ray* d_rays, int64_
                     sc.shade(),
                     sc.leaf(),
                     (uint32_t)(sc.n_wnodes4 * 16),
-                    (uint32_t)((sc.n_wnodes4 + sc.n_tris4) * 16),
+                    (uint32_t)(sc.rec_units() * 16),
                     sc.root,
                     sc.n_inner,
                     (sc.fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,

@@ -124,6 +124,7 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_refit_nodes", "rt_update_vertices", "rt_update_vertices_device", "rt_scene_bounds",
                "rt_last_update_timing", "rt_build_bvh", "rt_build_bvh_device", "rt_last_build_timing",
                "rt_build_scene", "rt_build_scene_device", "rt_last_scene_build_timing", "rt_refit_level_counts",
+               "rt_scene_walk_refs",
                "rt_scene_sah", "rt_trace_rays", "rt_trace_rays_device", "rt_last_query_timing",
                "rt_trace_rays_attr", "rt_trace_rays_attr_device"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
@@ -217,6 +218,7 @@ def lib() -> C.CDLL:
             "rt_build_scene_device": (C.c_int, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, i32, vp, vp]),
             "rt_last_scene_build_timing": (C.c_int, [vp, C.POINTER(f32)]),
             "rt_refit_level_counts": (C.c_int, [vp, C.POINTER(u32), i32, C.POINTER(i32)]),
+            "rt_scene_walk_refs": (C.c_int, [vp, i32, C.POINTER(u32), C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(u32)]),
             "rt_scene_sah": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
             "rt_trace_rays": (C.c_int, [vp, vp, C.c_int64, u32, vp]),
             "rt_trace_rays_device": (C.c_int, [vp, vp, C.c_int64, u32, vp, vp]),
@@ -711,6 +713,17 @@ class Renderer:
         _check(lib().rt_refit_level_counts(self._h, counts.ctypes.data_as(C.POINTER(C.c_uint32)), counts.size,
                                            C.byref(h)), self._h)
         return counts[:h.value]
+
+    def walk_refs(self, host_twin: bool = False):
+        """rt_scene_walk_refs: (words, root) -- the scene's walk references as the install derived them on
+        the device (two uint32 per inner record; empty when the scene has none), or with host_twin the
+        same from the device's records by the deriving kernel's host twin."""
+        n, root = C.c_uint64(), C.c_uint32()
+        _check(lib().rt_scene_walk_refs(self._h, int(host_twin), None, 0, C.byref(n), C.byref(root)), self._h)
+        words = np.zeros(max(n.value, 1), np.uint32)
+        _check(lib().rt_scene_walk_refs(self._h, int(host_twin), words.ctypes.data_as(C.POINTER(C.c_uint32)), words.size,
+                                        C.byref(n), C.byref(root)), self._h)
+        return words[:n.value], root.value
 
     def scene_sah(self) -> "SceneSah":
         """rt_scene_sah: the SAH cost of the scene as it stands on the GPU ->

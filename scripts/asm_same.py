@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Compares the device assembly of two builds function by function (make asm -> build/rt_render.s).
 
-    python3 scripts/asm_same.py PARENT.s THIS.s
+    python3 scripts/asm_same.py PARENT.s THIS.s [REGEX ...]
+
+Each REGEX is deleted from every line of THIS.s first: a change that only renames kernels (a new
+template parameter or argument type in the mangled names) is then compared under the parent's names.
 
 A function is the text from its `name:` label to its .Lfunc_end label.  Comments, blank lines and
 the numbers of local labels (.LBBn_m, .Ltmpn, .Lfunc_endn: they count functions of the whole file,
@@ -11,9 +14,11 @@ import re
 import sys
 
 
-def functions(path):
+def functions(path, strip=()):
     out, name, body = {}, None, []
     for line in open(path):
+        for rx in strip:
+            line = re.sub(rx, "", line)
         line = line.split(";", 1)[0].rstrip()
         if not line.strip():
             continue
@@ -31,7 +36,7 @@ def functions(path):
 
 
 def main():
-    a, b = functions(sys.argv[1]), functions(sys.argv[2])
+    a, b = functions(sys.argv[1]), functions(sys.argv[2], sys.argv[3:])
     gone = sorted(set(a) - set(b))
     new = sorted(set(b) - set(a))
     diff = sorted(k for k in a if k in b and a[k] != b[k])

@@ -137,17 +137,30 @@ def main():
 
 def ref_load_rule(loop):
     """DESIGN.md 7.2, one round trip per trip: from the trip's first record load on, in program order
-    (the inner step precedes the triangle step), the child-ref load (buffer_load_dwordx2 ... offset:48)
-    is issued before any s_waitcnt whose vmcnt is below the number of record loads issued so far, the
-    first wait that can hold the wave for this trip's records.  -> (holds, one line of text)."""
+    (the inner step precedes the triangle step), the child-ref load (buffer_load_dwordx2 ... offset:48, or
+    the cursor loop's load from the walk array, below) is issued before any s_waitcnt whose vmcnt is
+    below the number of record loads issued so far, the first wait that can hold the wave for this
+    trip's records.  -> (holds, one line of text)."""
     issued, started = 0, False
+    # The cursor loop (traverse_ifif's CUR) reads its child refs from the walk array, not from the
+    # record: its ref load is a buffer_load_dwordx2 with no offset whose address register was made by
+    # v_lshl_add_u32 ADDR, CUR, 1, WALK_OFF (walk_off + (cur << 1)) inside the trip; nothing else counts.
+    # (The waits the compiler leaves at that loop's head stand before the trip's first load and
+    # retire nothing of this trip: no wait before the first record load was ever counted.)
+    walk_addr = set()
     for l in loop:
         s = l.strip()
+        m = re.match(r"v_lshl_add_u32 (v\d+), (v\d+), 1, (v\d+)$", s)
+        # (after the trip's first record load, and of two different registers: the old decode's
+        # 3 x = (x << 1) + x names one register twice and stands before the loads)
+        if m and started and m.group(2) != m.group(3):
+            walk_addr.add(m.group(1))
         if s.startswith("buffer_load_dwordx4") and "offset:" not in s:
             started = True
         if not started:
             continue
-        if s.startswith("buffer_load_dwordx2") and "offset:48" in s:
+        m = re.match(r"buffer_load_dwordx2 v\[\d+:\d+\], (v\d+), ", s)
+        if (s.startswith("buffer_load_dwordx2") and "offset:48" in s) or (m and "offset:" not in s and m.group(1) in walk_addr):
             return True, f"ref load rule: holds (the ref load is record load {issued + 1} of the trip, no wait on them before it)"
         if s.startswith("buffer_load_"):
             issued += 1
