@@ -619,6 +619,51 @@ static_assert(sizeof(rt_hit_attr) == 64, "rt_hit_attr is 64 bytes");
 int rt_trace_rays_attr(rt_ctx* ctx, const rt_ray* rays, int64_t n, uint32_t flags, rt_hit_attr* hits);
 int rt_trace_rays_attr_device(rt_ctx* ctx, const rt_ray* d_rays, int64_t n, uint32_t flags, rt_hit_attr* d_hits, void* stream);
 
+/* Occlusion fans: n origins, each tested against the SAME k directions, answered with
+ * one bit per ray.  What occlusion and sky-visibility baking, light-probe visibility and shadowing by
+ * many distant lights ask: input is 32 n + 16 k bytes instead of 32 n k, output n k / 8 instead of 8 n k,
+ * n k may exceed a ray query's 2^30, and every traversal of a wave has one direction.
+ *
+ * With W = ceil(k / 32): ray (i, j) is {o_i, tmax_i, dirs[j].xyz}; dirs[j].w and `reserved` are ignored.
+ * Ray (i, j) is TRACED iff all of
+ *   1. it is a valid ray by rt_trace_rays' rule (finite origin and direction, non-zero direction,
+ *      tmax > 0.001f, no NaN tmax);
+ *   2. every component of n_i is finite;
+ *   3. n_i == (0, 0, 0) (either sign of zero: no culling for this origin), or
+ *      fmaf(nz, dz, fmaf(ny, dy, nx * dx)) > 0 on the RAW input words -- the caller's unnormalised d_j
+ *      and n_i, not the normalised direction -- so the rule is the same bits in every arithmetic and on
+ *      any host.
+ * Bit j & 31 of masks[(j >> 5) * n + i] is 1 iff ray (i, j) is traced and rt_trace_rays(...,
+ * RT_FLAG_ANY_HIT | flags) reports id >= 0 for it.  Every other bit of the W * n words is 0: rays not
+ * traced, the bits j >= k of the last chunk's words, the silent miss after a stack overflow.  The layout
+ * is chunk-major: the words of one 32-direction chunk for all origins are contiguous.
+ *
+ * flags: RT_FLAG_HW_MATH or RT_FLAG_STRICT_MATH (not both), RT_FLAG_EXACT_DIV; any other bit is
+ * RT_ERR_INVALID_ARG, RT_FLAG_ANY_HIT included (any hit is what a fan is).  Refused before any GPU work
+ * with RT_ERR_INVALID_ARG: a NULL ctx, n < 0 or n > 2^26, with n > 0 a k outside 1..RT_FAN_MAX_DIRS or a
+ * NULL pointer, a misaligned device pointer (origins and dirs 16 bytes, masks 4); RT_ERR_NO_SCENE without
+ * a scene.  n == 0 is RT_OK and launches nothing.
+ *
+ * Synchrony, the pinned-memory shortcut of the host form, stream and slot behaviour are
+ * rt_trace_rays[_device]'s: rt_trace_fan_device returns after enqueue, a scene replacement or vertex
+ * update called after it waits for the fan, and rt_last_query_timing, rt_last_deferred and
+ * rt_overflow_count cover a fan as they cover a query.
+ *
+ * rt_fan_expand (host only: no context, no GPU) is the definition in code: it writes the n * k rays in
+ * origin-major order (ray (i, j) at rays[i * k + j], reserved = 0) and traced[i * k + j] = 1 or 0.
+ * RT_ERR_INVALID_ARG for the same n, k and NULL pointers. */
+typedef struct rt_fan_origin { float ox, oy, oz, tmax; float nx, ny, nz; uint32_t reserved; } rt_fan_origin; /* 32 B */
+#define RT_FAN_MAX_DIRS 4096
+#ifdef __cplusplus
+static_assert(sizeof(rt_fan_origin) == 32, "rt_fan_origin is 32 bytes");
+#endif
+int rt_trace_fan(rt_ctx* ctx, const rt_fan_origin* origins, int64_t n, const rt_float4* dirs, int32_t k,
+                 uint32_t flags, uint32_t* masks);
+int rt_trace_fan_device(rt_ctx* ctx, const rt_fan_origin* d_origins, int64_t n, const rt_float4* d_dirs, int32_t k,
+                        uint32_t flags, uint32_t* d_masks, void* stream);
+int rt_fan_expand(const rt_fan_origin* origins, int64_t n, const rt_float4* dirs, int32_t k,
+                  rt_ray* rays, uint8_t* traced);
+
 /* Traversals of the last frame (or of the last ray query, if that came later) that outgrew the
  * fast kernel's LDS stack and restarted in-kernel with the general traversal (same result,
  * slower ray); diagnostics, synchronizes the stream. */

@@ -1267,4 +1267,64 @@ __global__ void __launch_bounds__(256, kMath == 2 ? RTK_QATTR_REF_WAVES : RTK_QA
     }
 }
 
+// ============================================================================
+// Occlusion fans (rt_trace_fan, DESIGN.md 21): n origins against the same k directions, one bit per
+// ray.  query_kernel's persistent grid, stack columns, trace<> instantiation (any hit) and restart
+// value; a work item is (group g of 64 consecutive origins, chunk c of 32 directions), items in
+// origin-group-major order so that the waves at work at one time are near each other in the scene.
+// Lane = origin: it loads its record once per item as two 16-B loads and walks the chunk's
+// directions, whose loads are wave-uniform, so every traversal of the wave has ONE direction (in
+// S_ref: one octant loop, unless a component is zero).  Per direction a lane whose ray is not traced
+// -- rt_fan_expand's rule: query_ray_ok, a finite normal, and a zero normal or dot(n, d) > 0 on the
+// raw words -- sits the traversal out as query_kernel's invalid lanes do, and a direction no lane of
+// the wave is traced for is skipped.  The hit bits gather in a register and the lane stores its one
+// word after the chunk (a wave's 256 B are contiguous: the layout is chunk-major); every mask word
+// has exactly one writer.  Each ray is ray_init(o, d_j) by the frame's own function, per lane: the
+// bits are the expanded query's by construction.
+// ============================================================================
+template <bool FASTONLY>
+__global__ void __launch_bounds__(256, kMath == 2 ? RTK_FAN_REF_WAVES : RTK_FAN_WAVES) fan_kernel(DevScene S, Outputs O, rtk::Fan Fn) {
+    __shared__ uint32_t s_stack[4][rtk::kLdsRows][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t nitems = ((Fn.n + rtk::kSegRays - 1) / rtk::kSegRays) * Fn.chunks;
+    uint32_t home = blockIdx.x & (rtk::kCursors - 1u);
+    Stack st;
+    st.lds = &s_stack[wave][rtk::kLdsGuard][lane];
+    st.glb = O.gstack + ((size_t)blockIdx.x * rtk::kBlockThreads + threadIdx.x);
+    st.gstride = O.local_pixels;   // the lanes launched
+    for (;;) {
+        const uint32_t item = rtk::grab_group(Fn.fetch, nitems, home);
+        if (item == rtk::kNoGroup) break;
+        const uint32_t g = item / Fn.chunks, c = item - g * Fn.chunks;
+        const uint32_t i = g * rtk::kSegRays + (uint32_t)lane;
+        const bool inside = i < Fn.n;   // (false only in the last group's tail)
+        float4 a = make_float4(0, 0, 0, 0), b = a;
+        if (inside) {
+            const float4* op = Fn.origins + (size_t)i * 2;
+            a = op[0];
+            b = op[1];
+        }
+        const F3 nrm = F3{b.x, b.y, b.z};
+        const bool nfin = fabsf(b.x) < __builtin_inff() && fabsf(b.y) < __builtin_inff() && fabsf(b.z) < __builtin_inff();
+        const bool nocull = b.x == 0.0f && b.y == 0.0f && b.z == 0.0f;
+        const uint32_t j0 = c * 32u, j1 = min(j0 + 32u, Fn.k);
+        uint32_t bits = 0u, overflows = 0u;
+        for (uint32_t j = j0; j < j1; ++j) {
+            const float4 d = Fn.dirs[j];   // wave-uniform
+            const bool traced = inside && nfin && query_ray_ok(a, d) && (nocull || dot(nrm, F3{d.x, d.y, d.z}) > 0.0f);
+            if (__builtin_amdgcn_ballot_w64(traced) == 0) continue;
+            if (traced) {
+                Ray ray = ray_init(F3{a.x, a.y, a.z}, F3{d.x, d.y, d.z});
+                float t = a.w;
+                bool overflow = false;
+                const int hit = trace<false, FASTONLY, 0, true, true, kOctLoops>(S, O, ray, t, st, overflow, a.w);
+                if (hit >= 0) bits |= 1u << (j & 31u);
+                if (overflow) ++overflows;
+            }
+        }
+        if (inside) Fn.masks[(size_t)c * Fn.n + i] = bits;
+        if (overflows) atomicAdd(O.overflow, (unsigned long long)overflows);
+    }
+}
+
 }  // namespace RTK_NS

@@ -85,6 +85,12 @@
 #ifndef RTK_QATTR_WAVES
 #define RTK_QATTR_WAVES 7       // the same for S_strict / S_hw
 #endif
+#ifndef RTK_FAN_REF_WAVES
+#define RTK_FAN_REF_WAVES 8     // waves per SIMD the S_ref fan kernels are bounded to (no scratch: DESIGN.md 21)
+#endif
+#ifndef RTK_FAN_WAVES
+#define RTK_FAN_WAVES 6         // the same for S_strict / S_hw: at 7 their fast kernels spill 12 / 24 B
+#endif
 #ifndef RTK_QUERY_GRID_PCT
 #define RTK_QUERY_GRID_PCT 75   // persistent query grid, percent of the blocks the chip holds at once (C3's 2.07 M primary
                                 // rays, closest hit / incoherent rays: 50 % 0.248 / 0.955 ms, 75 % 0.232 / 0.998, 100 % 0.242 /
@@ -229,6 +235,18 @@ struct Query {
     uint2* hits;
     uint32_t n;
     uint32_t* fetch;    // the launch's work cursors (grab_group), zeroed before it
+};
+
+// An occlusion fan's launch (rt_trace_fan, fan_kernel): origins are rt_fan_origin as two float4 {o.xyz,
+// tmax}, {n.xyz, reserved}, dirs float4 {d.xyz, -}, masks one word per origin and 32-direction chunk,
+// chunk-major (word (c, i) at c * n + i).  n <= 2^26 and k <= 4096, so the work items -- (64-origin
+// group, chunk) pairs, ceil(n / 64) * chunks <= 2^27 -- fit grab_group's 32 bits.
+struct Fan {
+    const float4* origins;
+    const float4* dirs;
+    uint32_t* masks;
+    uint32_t n, k, chunks;   // chunks = ceil(k / 32)
+    uint32_t* fetch;         // the launch's work cursors (grab_group), zeroed before it
 };
 
 struct Outputs {
@@ -1148,6 +1166,11 @@ struct rt_ctx {
     int query_grid[2][3] = {{0, 0, 0}, {0, 0, 0}};   // [record kind][math]
     float4* d_qrays = nullptr; size_t qrays_cap = 0;
     uint2* d_qhits = nullptr; size_t qhits_cap = 0;
+    // occlusion fans: the persistent grid per math mode, the host form's direction table
+    // (its origins and masks go through d_qrays and d_qhits), RTAMD_FAN_GRID_BLOCKS (-1: not read yet)
+    int fan_grid[3] = {0, 0, 0};
+    float4* d_fdirs = nullptr; size_t fdirs_cap = 0;
+    int fan_grid_cap = -1;
     FrameSlot* query_slot = nullptr;
     bool query_last = false;
     struct { bool on = false; unsigned long long* d_counts = nullptr; } trace;   // rt_fetch_counts
@@ -1471,6 +1494,7 @@ template <int M> struct Kernels;
             return any ? (fast ? (void*)NS::query_attr_kernel<true, true> : (void*)NS::query_attr_kernel<true, false>) \
                        : (fast ? (void*)NS::query_attr_kernel<false, true> : (void*)NS::query_attr_kernel<false, false>); \
         }                                                                                                  \
+        static void* fan(bool fast) { return fast ? (void*)NS::fan_kernel<true> : (void*)NS::fan_kernel<false>; } \
         static void* batch(bool fast, bool next) {                                                         \
             return fast ? (next ? (void*)NS::first_bounce_batch_kernel<true, true> : (void*)NS::first_bounce_batch_kernel<true, false>) \
                         : (next ? (void*)NS::first_bounce_batch_kernel<false, true> : (void*)NS::first_bounce_batch_kernel<false, false>); \
@@ -1504,6 +1528,9 @@ static void* kernel_query(int m, bool any, bool fast) {
 }
 static void* kernel_query_attr(int m, bool any, bool fast) {
     return m == 0 ? Kernels<0>::query_attr(any, fast) : m == 1 ? Kernels<1>::query_attr(any, fast) : Kernels<2>::query_attr(any, fast);
+}
+static void* kernel_fan(int m, bool fast) {
+    return m == 0 ? Kernels<0>::fan(fast) : m == 1 ? Kernels<1>::fan(fast) : Kernels<2>::fan(fast);
 }
 // the timeline instantiation (rt_wave_timeline): S_ref, the fast kernels
 static void* kernel_timeline_first(bool next, bool walk) {
@@ -1720,6 +1747,7 @@ int rt_destroy(rt_ctx* c) {
     if (c->d_overflow) (void)hipFree(c->d_overflow);
     if (c->d_qrays) (void)hipFree(c->d_qrays);
     if (c->d_qhits) (void)hipFree(c->d_qhits);
+    if (c->d_fdirs) (void)hipFree(c->d_fdirs);
     for (auto& f : c->slots) free_slot(f);
     for (auto& o : c->orders) (void)hipFree(o.d);
     if (c->tline.d_words) (void)hipFree(c->tline.d_words);
@@ -3015,6 +3043,141 @@ int rt_trace_rays_attr_device(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32
 
 int rt_trace_rays_attr(rt_ctx* c, const rt_ray* rays, int64_t n, uint32_t flags, rt_hit_attr* hits) {
     return trace_rays_host(c, kQueryAttr, "rt_trace_rays_attr", rays, n, flags, hits);
+}
+
+// ---- occlusion fans ----
+// A fan is a query to everything that waits for or reports on one: it takes the stream's kQueryKey slot
+// (spill columns, cursors, restart count, events, idle record) and becomes the context's last query.
+constexpr int64_t kMaxFanOrigins = 1ll << 26;
+constexpr uint32_t kFanFlags = RT_FLAG_HW_MATH | RT_FLAG_STRICT_MATH | RT_FLAG_EXACT_DIV;
+
+// the refusals that need no GPU; `who` names the entry point in the message
+static int fan_check(rt_ctx* c, const char* who, const void* origins, int64_t n, const void* dirs, int32_t k, uint32_t flags,
+                     const void* masks) {
+    if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
+    if (n < 0 || n > kMaxFanOrigins) return set_err(c, std::string(who) + ": n must be 0..2^26", RT_ERR_INVALID_ARG);
+    if (n > 0 && (k < 1 || k > RT_FAN_MAX_DIRS))
+        return set_err(c, std::string(who) + ": k must be 1..RT_FAN_MAX_DIRS", RT_ERR_INVALID_ARG);
+    if (n > 0 && (!origins || !dirs || !masks)) return set_err(c, std::string(who) + ": origins, dirs or masks is NULL", RT_ERR_INVALID_ARG);
+    if (flags & ~kFanFlags) return set_err(c, std::string(who) + ": a flag that is not a fan's", RT_ERR_INVALID_ARG);
+    if ((flags & RT_FLAG_STRICT_MATH) && (flags & RT_FLAG_HW_MATH))
+        return set_err(c, std::string(who) + ": RT_FLAG_STRICT_MATH and RT_FLAG_HW_MATH exclude each other", RT_ERR_INVALID_ARG);
+    if (!c->have_scene) return set_err(c, std::string(who) + ": no scene uploaded", RT_ERR_NO_SCENE);
+    return RT_OK;
+}
+
+// checked arguments, n > 0
+static int fan_enqueue(rt_ctx* c, const rt_fan_origin* d_origins, int64_t n, const rt_float4* d_dirs, int32_t k, uint32_t flags,
+                       uint32_t* d_masks, hipStream_t s) {
+    int rc = RT_OK;
+    rt_ctx::FrameSlot* Lp = nullptr;
+    if ((rc = slot_for(c, (void*)s, kQueryKey, &Lp))) return rc;
+    rt_ctx::FrameSlot& L = *Lp;
+    const int math = (flags & RT_FLAG_STRICT_MATH) ? 0 : (flags & RT_FLAG_HW_MATH) ? 1 : 2;
+    const Scene& sc = c->scene;
+    rtk::DevScene S{sc.wnodes(),
+                    sc.tris(),
+                    sc.shade(),
+                    sc.leaf(),
+                    (uint32_t)(sc.n_wnodes4 * 16),
+                    (uint32_t)(sc.rec_units() * 16),
+                    sc.root,
+                    sc.n_inner,
+                    (sc.fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,
+                    sc.clean};
+    const bool fast = S.clean != 0 && !sc.split;   // as for queries and frames
+    if (c->fan_grid_cap < 0) {   // RTAMD_FAN_GRID_BLOCKS=<b> (tests): at most b blocks, so that a wave takes many items
+        const char* v = std::getenv("RTAMD_FAN_GRID_BLOCKS");
+        const long b = v ? std::strtol(v, nullptr, 10) : 0;
+        c->fan_grid_cap = b > 0 && b < (1l << 20) ? (int)b : 0;
+    }
+    int& fgrid = c->fan_grid[math];
+    if (!fgrid) {
+        int cus = 0, b1 = 0;
+        HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, (const void*)kernel_fan(math, true), 256, 0));
+        fgrid = std::max(8, std::max(b1, 1) * cus * RTK_QUERY_GRID_PCT / 100);
+        if (c->fan_grid_cap) fgrid = std::min(fgrid, c->fan_grid_cap);
+    }
+    // the stack columns are sized for the mode's whole grid, whatever n and k are (ensure keeps a larger
+    // allocation, so fans and queries share the slot's columns)
+    const size_t full = (size_t)fgrid;
+    const uint32_t chunks = ((uint32_t)k + 31u) / 32u;
+    const uint32_t items = (uint32_t)((n + rtk::kSegRays - 1) / rtk::kSegRays) * chunks;   // <= 2^27
+    const uint32_t grid = (uint32_t)std::min<size_t>(full, (items + 3u) / 4u);
+    if ((rc = ensure(c, L.d_gstack, L.gstack_cap, full * rtk::kBlockThreads * rtk::kGlobalStack))) return rc;
+    if (!L.d_qcnt) {
+        size_t cap = 0;
+        if ((rc = ensure(c, L.d_qcnt, cap, rtk::kCursorSet + 32))) return rc;
+    }
+    for (hipEvent_t& e : L.qev)
+        if (!e) HIPC(c, hipEventCreate(&e));
+    rtk::Outputs O{};
+    O.gstack = L.d_gstack;
+    O.overflow = c->d_overflow;
+    O.restarts = L.d_qcnt + rtk::kCursorSet;
+    O.local_pixels = (uint64_t)grid * rtk::kBlockThreads;   // the stack's stride: the lanes launched
+    rtk::Fan Fn{(const float4*)d_origins, (const float4*)d_dirs, d_masks, (uint32_t)n, (uint32_t)k, chunks, L.d_qcnt};
+    HIPC(c, hipMemsetAsync(L.d_qcnt, 0, (rtk::kCursorSet + 32) * sizeof(uint32_t), s));
+    (void)hipGetLastError();
+    void* args[] = {&S, &O, &Fn};
+    HIPC(c, hipExtLaunchKernel(kernel_fan(math, fast), dim3(grid), dim3(rtk::kBlockThreads), args, 0, s, L.qev[0], L.qev[1], 0));
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(L.idle, s));
+    c->query_slot = &L;
+    c->query_last = true;
+    return RT_OK;
+}
+
+int rt_trace_fan_device(rt_ctx* c, const rt_fan_origin* d_origins, int64_t n, const rt_float4* d_dirs, int32_t k, uint32_t flags,
+                        uint32_t* d_masks, void* stream) {
+    if (const int rc = fan_check(c, "rt_trace_fan_device", d_origins, n, d_dirs, k, flags, d_masks)) return rc;
+    if (n == 0) return RT_OK;
+    if (((uintptr_t)d_origins & 15u) || ((uintptr_t)d_dirs & 15u) || ((uintptr_t)d_masks & 3u))
+        return set_err(c, "rt_trace_fan_device: d_origins and d_dirs must be 16-byte aligned and d_masks 4-byte aligned",
+                       RT_ERR_INVALID_ARG);
+    HIPC(c, hipSetDevice(c->device));
+    return fan_enqueue(c, d_origins, n, d_dirs, k, flags, d_masks, stream ? (hipStream_t)stream : c->stream);
+}
+
+int rt_trace_fan(rt_ctx* c, const rt_fan_origin* origins, int64_t n, const rt_float4* dirs, int32_t k, uint32_t flags,
+                 uint32_t* masks) {
+    if (const int rc = fan_check(c, "rt_trace_fan", origins, n, dirs, k, flags, masks)) return rc;
+    if (n == 0) return RT_OK;
+    HIPC(c, hipSetDevice(c->device));
+    // pinned, device-mapped caller memory is used directly, anything else is staged: as rt_trace_rays
+    auto mapped = [](const void* p, size_t align) -> void* {
+        hipPointerAttribute_t pa;
+        if (hipPointerGetAttributes(&pa, p) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer &&
+            !((uintptr_t)pa.devicePointer & (align - 1)))
+            return pa.devicePointer;
+        (void)hipGetLastError();   // pageable memory: not an error
+        return nullptr;
+    };
+    const size_t words = (size_t)(((uint32_t)k + 31u) / 32u) * (size_t)n;
+    const rt_fan_origin* d_origins = (const rt_fan_origin*)mapped(origins, 16);
+    const rt_float4* d_dirs = (const rt_float4*)mapped(dirs, 16);
+    uint32_t* d_masks = (uint32_t*)mapped(masks, 4);
+    int rc = RT_OK;
+    if (!d_origins) {
+        if ((rc = ensure(c, c->d_qrays, c->qrays_cap, (size_t)n * 2))) return rc;
+        HIPC(c, hipMemcpyAsync(c->d_qrays, origins, (size_t)n * sizeof(rt_fan_origin), hipMemcpyHostToDevice, c->stream));
+        d_origins = (const rt_fan_origin*)c->d_qrays;
+    }
+    if (!d_dirs) {
+        if ((rc = ensure(c, c->d_fdirs, c->fdirs_cap, (size_t)k))) return rc;
+        HIPC(c, hipMemcpyAsync(c->d_fdirs, dirs, (size_t)k * sizeof(rt_float4), hipMemcpyHostToDevice, c->stream));
+        d_dirs = (const rt_float4*)c->d_fdirs;
+    }
+    const bool back = !d_masks;
+    if (back) {   // d_qhits counts 8-B words
+        if ((rc = ensure(c, c->d_qhits, c->qhits_cap, (words + 1) / 2))) return rc;
+        d_masks = (uint32_t*)c->d_qhits;
+    }
+    if ((rc = fan_enqueue(c, d_origins, n, d_dirs, k, flags, d_masks, c->stream))) return rc;
+    if (back) HIPC(c, hipMemcpyAsync(masks, d_masks, words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, wait_ctx(c, c->stream));
+    return RT_OK;
 }
 
 int rt_last_query_timing(rt_ctx* c, float* ms) {

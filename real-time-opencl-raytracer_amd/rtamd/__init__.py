@@ -37,6 +37,7 @@ RT_FLAG_WF_SORT = 32
 RT_FLAG_STRICT_MATH = 64
 RT_FLAG_ANY_HIT = 128          # trace_rays only: the first accepted triangle instead of the closest
 RT_RAY_TMAX_DEFAULT = 4294967296.0   # HitRecordInit: t = UINT_MAX as float
+RT_FAN_MAX_DIRS = 4096         # trace_fan: directions per call
 RT_MAX_DEPTH = 8
 RT_BUILD_EXTENT_KEYS = 0x100   # ORed into a builder's max_leaf: extent-aware Morton keys
 RT_MAX_BATCH = int(os.environ.get("RTAMD_MAX_BATCH", "8"))   # rt_render_device_batch frames per launch (RTAMD_MAX_BATCH: an A/B build's)
@@ -72,6 +73,11 @@ class rt_ray(C.Structure):
                 ("dx", C.c_float), ("dy", C.c_float), ("dz", C.c_float), ("reserved", C.c_uint32)]
 
 
+class rt_fan_origin(C.Structure):
+    _fields_ = [("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float), ("tmax", C.c_float),
+                ("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float), ("reserved", C.c_uint32)]
+
+
 class rt_hit(C.Structure):
     _fields_ = [("id", C.c_int32), ("t", C.c_float)]
 
@@ -86,6 +92,7 @@ class rt_hit_attr(C.Structure):
 # the same records as numpy dtypes (trace_rays' and trace_rays_attr's buffers)
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("reserved", np.uint32)])
 HIT_DTYPE = np.dtype([("id", np.int32), ("t", np.float32)])
+FAN_ORIGIN_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("n", np.float32, 3), ("reserved", np.uint32)])
 HIT_ATTR_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32),
                            ("p", np.float32, 3), ("ndotd", np.float32),
                            ("ng", np.float32, 3), ("reserved0", np.uint32),
@@ -126,7 +133,8 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_build_scene", "rt_build_scene_device", "rt_last_scene_build_timing", "rt_refit_level_counts",
                "rt_scene_walk_refs",
                "rt_scene_sah", "rt_trace_rays", "rt_trace_rays_device", "rt_last_query_timing",
-               "rt_trace_rays_attr", "rt_trace_rays_attr_device"]
+               "rt_trace_rays_attr", "rt_trace_rays_attr_device",
+               "rt_trace_fan", "rt_trace_fan_device", "rt_fan_expand"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
                 "rt_mesh_load_dae", "rt_mesh_save_dae",
                 "rt_mesh_gen_cornell", "rt_mesh_gen_torus_knot", "rt_mesh_gen_heightfield", "rt_mesh_gen_random",
@@ -225,6 +233,9 @@ def lib() -> C.CDLL:
             "rt_trace_rays_attr": (C.c_int, [vp, vp, C.c_int64, u32, vp]),
             "rt_trace_rays_attr_device": (C.c_int, [vp, vp, C.c_int64, u32, vp, vp]),
             "rt_last_query_timing": (C.c_int, [vp, C.POINTER(f32)]),
+            "rt_trace_fan": (C.c_int, [vp, vp, C.c_int64, vp, i32, u32, vp]),
+            "rt_trace_fan_device": (C.c_int, [vp, vp, C.c_int64, vp, i32, u32, vp, vp]),
+            "rt_fan_expand": (C.c_int, [vp, C.c_int64, vp, i32, vp, vp]),
             "rt_bvh_build_lbvh": (C.c_int, [vp, i32, C.POINTER(vp)]),
             "rt_mesh_create": (vp, []),
             "rt_mesh_destroy": (None, [vp]),
@@ -299,6 +310,70 @@ def pack_rays(origins, directions, tmax=None) -> np.ndarray:
             raise ValueError("pack_rays: tmax has another length than the rays")
         rays["tmax"].view(np.uint32)[...] = t.view(np.uint32)
     return rays
+
+
+def pack_fan_origins(origins, normals=None, tmax=None) -> np.ndarray:
+    """n rt_fan_origin records (FAN_ORIGIN_DTYPE) from float32 (n, 3) origins, normals (None = zero:
+    no culling) and tmax (None = RT_RAY_TMAX_DEFAULT, a scalar, or float32[n], whose bits are kept)."""
+    o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    rec = np.zeros(o.shape[0], FAN_ORIGIN_DTYPE)
+    rec["o"] = o
+    if normals is not None:
+        nr = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if nr.shape != o.shape:
+            raise ValueError("pack_fan_origins: origins and normals differ in shape")
+        rec["n"] = nr
+    if tmax is None:
+        rec["tmax"] = np.float32(RT_RAY_TMAX_DEFAULT)
+    elif np.ndim(tmax) == 0:
+        rec["tmax"] = np.float32(tmax)
+    else:
+        t = np.ascontiguousarray(tmax, dtype=np.float32).reshape(-1)
+        if t.shape[0] != o.shape[0]:
+            raise ValueError("pack_fan_origins: tmax has another length than the origins")
+        rec["tmax"].view(np.uint32)[...] = t.view(np.uint32)
+    return rec
+
+
+def pack_fan_dirs(directions) -> np.ndarray:
+    """k rt_float4 {d.xyz, 0} as float32 (k, 4) from float32 (k, 3) or (k, 4) directions."""
+    d = np.ascontiguousarray(directions, dtype=np.float32)
+    d = d.reshape(-1, 4 if d.ndim == 2 and d.shape[1] == 4 else 3)
+    out = np.zeros((d.shape[0], 4), np.float32)
+    out[:, :d.shape[1]] = d
+    return out
+
+
+def fan_bits(masks, k: int) -> np.ndarray:
+    """trace_fan's uint32[W, n] masks as bool[n, k]: [i, j] = ray (i, j) is occluded."""
+    m = np.ascontiguousarray(masks, dtype=np.uint32)
+    j = np.arange(k)
+    return ((m[j >> 5, :] >> (j & 31).astype(np.uint32)[:, None]) & 1).astype(bool).T.copy()
+
+
+def fan_pack(bits) -> np.ndarray:
+    """The inverse of fan_bits: bool[n, k] -> uint32[ceil(k / 32), n], unused bits 0."""
+    b = np.ascontiguousarray(bits, dtype=bool)
+    n, k = b.shape
+    w = (k + 31) // 32
+    padded = np.zeros((n, w * 32), np.uint32)
+    padded[:, :k] = b
+    weights = (np.uint32(1) << np.arange(32, dtype=np.uint32))
+    return np.ascontiguousarray((padded.reshape(n, w, 32) * weights).sum(axis=2, dtype=np.uint32).T)
+
+
+def fan_expand(origins, directions, normals=None, tmax=None):
+    """rt_fan_expand: the fan's n * k rays in origin-major order (RAY_DTYPE[n * k], ray (i, j) at
+    i * k + j) and which of them the fan traces (bool[n * k]); host only.  `origins` may be packed
+    FAN_ORIGIN_DTYPE records (then normals and tmax are theirs)."""
+    rec = origins if getattr(origins, "dtype", None) == FAN_ORIGIN_DTYPE else pack_fan_origins(origins, normals, tmax)
+    rec = np.ascontiguousarray(rec)
+    d = pack_fan_dirs(directions)
+    n, k = rec.shape[0], d.shape[0]
+    rays = np.zeros(n * k, RAY_DTYPE)
+    traced = np.zeros(n * k, np.uint8)
+    _check(lib().rt_fan_expand(_ptr(rec), n, _ptr(d), k, _ptr(rays), _ptr(traced)))
+    return rays, traced.astype(bool)
 
 
 def params_to_array(p: rt_params) -> np.ndarray:
@@ -955,8 +1030,32 @@ class Renderer:
                                                flags | (RT_FLAG_ANY_HIT if any_hit else 0), C.c_void_p(d_hits or None),
                                                C.c_void_p(stream or None)), self._h)
 
+    def trace_fan(self, origins, directions, normals=None, tmax=None, flags: int = 0) -> np.ndarray:
+        """rt_trace_fan: n origins against the same k directions, one occlusion bit per ray ->
+        uint32[W, n], W = ceil(k / 32): bit j & 31 of [j >> 5, i] is set iff ray (o_i, d_j) within
+        tmax_i is traced and hits anything (fan_bits unpacks it).  A ray is not traced (bit 0) where
+        it is invalid or where the origin's normal is non-zero and dot(n_i, d_j) <= 0 on the raw
+        words; normals None = no culling.  `origins` may be packed FAN_ORIGIN_DTYPE records.
+        flags: a math flag, RT_FLAG_EXACT_DIV."""
+        rec = origins if getattr(origins, "dtype", None) == FAN_ORIGIN_DTYPE else pack_fan_origins(origins, normals, tmax)
+        rec = np.ascontiguousarray(rec)
+        d = pack_fan_dirs(directions)
+        n, k = rec.shape[0], d.shape[0]
+        masks = np.zeros(((k + 31) // 32, n), np.uint32)
+        _check(lib().rt_trace_fan(self._h, _ptr(rec), n, _ptr(d), k, flags, _ptr(masks)), self._h)
+        return masks
+
+    def trace_fan_device(self, d_origins: int, n: int, d_dirs: int, k: int, d_masks: int, flags: int = 0,
+                         stream: Optional[int] = None) -> None:
+        """rt_trace_fan_device: n rt_fan_origin at d_origins and k rt_float4 at d_dirs (16-byte aligned)
+        -> ceil(k / 32) * n uint32 at d_masks, enqueued on `stream` (None = the ctx's own); returns
+        after enqueue."""
+        _stream_arg(stream)
+        _check(lib().rt_trace_fan_device(self._h, C.c_void_p(d_origins or None), n, C.c_void_p(d_dirs or None), k, flags,
+                                         C.c_void_p(d_masks or None), C.c_void_p(stream or None)), self._h)
+
     def last_query_ms(self) -> float:
-        """rt_last_query_timing: kernel time of the last ray query of either kind (ms)."""
+        """rt_last_query_timing: kernel time of the last ray query of either kind, or fan (ms)."""
         ms = C.c_float()
         _check(lib().rt_last_query_timing(self._h, C.byref(ms)), self._h)
         return ms.value
