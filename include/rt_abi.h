@@ -664,6 +664,48 @@ int rt_trace_fan_device(rt_ctx* ctx, const rt_fan_origin* d_origins, int64_t n, 
 int rt_fan_expand(const rt_fan_origin* origins, int64_t n, const rt_float4* dirs, int32_t k,
                   rt_ray* rays, uint8_t* traced);
 
+/* ---- closest-point queries ----
+ * For n caller-supplied points, the nearest triangle of the uploaded scene within the point's search
+ * radius r: its id (3 * index, as rt_hit's), the squared distance d2, the barycentrics (u, v) of the
+ * closest point (1 - u - v) p0 + u p1 + v p2 (rt_hit_attr's convention) and the point itself.  The
+ * scene is the one rays see: after rt_update_vertices[_device] the moved mesh.
+ *
+ * A point is VALID iff x, y, z are finite and r > 0 (+inf is legal; NaN, 0, -0 and negatives are
+ * not); an invalid point is a miss.  A miss is {id = -1, d2 = +inf, every other word 0}.  There is
+ * ONE arithmetic, single IEEE binary32 operations on every host and on the device (Ericson's
+ * point-triangle regions on the record's p0, e1 = fl(p1 - p0), e2 = fl(p2 - p0); DESIGN.md 22 has the
+ * text): triangle id replaces the current answer iff d2 < best, or d2 == best and id is lower, with
+ * best starting at r * r.  So r is exclusive, among equally near triangles the lowest id wins, and
+ * on a tree whose boxes contain their triangles the record is the minimum over ALL triangles,
+ * whatever the tree.  A query that would push a 65th stack entry ends as a miss and is counted once
+ * by rt_overflow_count, as a ray's; one that meets a malformed inner node ends as a miss.
+ *
+ * flags must be 0: any bit is RT_ERR_INVALID_ARG.  Refused before any GPU work with
+ * RT_ERR_INVALID_ARG: a NULL ctx, n < 0 or n > 2^30, a NULL pointer with n > 0, a device pointer not
+ * 16-byte aligned; RT_ERR_NO_SCENE without a scene.  n == 0 is RT_OK and launches nothing.
+ *
+ * Synchrony, the pinned-memory shortcut of the host form, stream and slot behaviour are
+ * rt_trace_rays[_device]'s: rt_closest_points_device returns after enqueue, a scene replacement or
+ * vertex update called after it waits for the query, rt_last_query_timing reports its kernel time and
+ * rt_last_deferred 0 after it.
+ *
+ * rt_closest_points_host (host only: no context, no GPU) is the definition in code, over
+ * rt_upload_scene's arrays: the device computes the same 8 words per point.  stats3: NULL, or three
+ * counters {overflows, inner visits, triangle tests} of the call.  RT_ERR_INVALID_ARG for a NULL or
+ * empty array, nidx % 3 or n outside 0..2^30; RT_ERR_BAD_SCENE as rt_upload_scene (an index out of
+ * range, a cycle, a leaf range past the references). */
+typedef struct rt_point { float x, y, z, r; } rt_point;                                            /* 16 B */
+typedef struct rt_closest { int32_t id; float d2, u, v; float px, py, pz; uint32_t reserved; } rt_closest; /* 32 B */
+#ifdef __cplusplus
+static_assert(sizeof(rt_point) == 16 && sizeof(rt_closest) == 32, "rt_point is 16 bytes, rt_closest 32");
+#endif
+int rt_closest_points(rt_ctx* ctx, const rt_point* pts, int64_t n, uint32_t flags, rt_closest* out);
+int rt_closest_points_device(rt_ctx* ctx, const rt_point* d_pts, int64_t n, uint32_t flags, rt_closest* d_out,
+                             void* stream);
+int rt_closest_points_host(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx,
+                           const rt_bvh_node* nodes, int32_t nn, const int32_t* refs, int32_t nref,
+                           const rt_point* pts, int64_t n, rt_closest* out, uint64_t* stats3);
+
 /* Traversals of the last frame (or of the last ray query, if that came later) that outgrew the
  * fast kernel's LDS stack and restarted in-kernel with the general traversal (same result,
  * slower ray); diagnostics, synchronizes the stream. */

@@ -56,6 +56,7 @@
 #include "rt_lbvh.h"
 #include "rt_scene_build.h"
 #include "rt_sah.h"
+#include "rt_closest.h"
 #include "lbvh_core.hpp"
 
 #ifndef RTK_WF_WAVES
@@ -1171,6 +1172,10 @@ struct rt_ctx {
     int fan_grid[3] = {0, 0, 0};
     float4* d_fdirs = nullptr; size_t fdirs_cap = 0;
     int fan_grid_cap = -1;
+    // closest-point queries: the persistent grid, RTAMD_CLOSEST_GRID_BLOCKS (-1: not read yet);
+    // the host form's points and records go through d_qrays and d_qhits
+    int closest_grid = 0;
+    int closest_grid_cap = -1;
     FrameSlot* query_slot = nullptr;
     bool query_last = false;
     struct { bool on = false; unsigned long long* d_counts = nullptr; } trace;   // rt_fetch_counts
@@ -3176,6 +3181,108 @@ int rt_trace_fan(rt_ctx* c, const rt_fan_origin* origins, int64_t n, const rt_fl
     }
     if ((rc = fan_enqueue(c, d_origins, n, d_dirs, k, flags, d_masks, c->stream))) return rc;
     if (back) HIPC(c, hipMemcpyAsync(masks, d_masks, words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, wait_ctx(c, c->stream));
+    return RT_OK;
+}
+
+// ---- closest-point queries ----
+// A point query is a query to everything that waits for or reports on one, as a fan is: it takes the
+// stream's kQueryKey slot (spill columns, cursors, restart count, events, idle record) and becomes the
+// context's last query.  Its kernel (rt_closest.hip) restarts nothing: the slot's restart count stays 0.
+static_assert(rtclosest::kThreads == rtk::kBlockThreads && rtclosest::kGlobalStack == rtk::kGlobalStack &&
+                  rtclosest::kCursors == rtk::kCursors && rtclosest::kCursorStride == rtk::kCursorStride,
+              "rt_closest.hip shares the query slot's spill columns and cursors");
+
+// the refusals that need no GPU; `who` names the entry point in the message
+static int closest_check(rt_ctx* c, const char* who, const void* pts, int64_t n, uint32_t flags, const void* out) {
+    if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
+    if (n < 0 || n > kMaxQueryRays) return set_err(c, std::string(who) + ": n must be 0..2^30", RT_ERR_INVALID_ARG);
+    if (n > 0 && (!pts || !out)) return set_err(c, std::string(who) + ": pts or out is NULL", RT_ERR_INVALID_ARG);
+    if (flags) return set_err(c, std::string(who) + ": flags must be 0", RT_ERR_INVALID_ARG);
+    if (!c->have_scene) return set_err(c, std::string(who) + ": no scene uploaded", RT_ERR_NO_SCENE);
+    return RT_OK;
+}
+
+// checked arguments, n > 0
+static int closest_enqueue(rt_ctx* c, const rt_point* d_pts, int64_t n, rt_closest* d_out, hipStream_t s) {
+    int rc = RT_OK;
+    rt_ctx::FrameSlot* Lp = nullptr;
+    if ((rc = slot_for(c, (void*)s, kQueryKey, &Lp))) return rc;
+    rt_ctx::FrameSlot& L = *Lp;
+    const Scene& sc = c->scene;
+    if (c->closest_grid_cap < 0) {   // RTAMD_CLOSEST_GRID_BLOCKS=<b> (tests): at most b blocks, so that a wave takes many groups
+        const char* v = std::getenv("RTAMD_CLOSEST_GRID_BLOCKS");
+        const long b = v ? std::strtol(v, nullptr, 10) : 0;
+        c->closest_grid_cap = b > 0 && b < (1l << 20) ? (int)b : 0;
+    }
+    int& cgrid = c->closest_grid;
+    if (!cgrid) {
+        int cus = 0, b1 = 0;
+        HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, rtclosest::kernel(), rtclosest::kThreads, 0));
+        cgrid = std::max(8, std::max(b1, 1) * cus * RTK_QUERY_GRID_PCT / 100);
+        if (c->closest_grid_cap) cgrid = std::min(cgrid, c->closest_grid_cap);
+    }
+    // the stack columns are sized for the whole grid, whatever n is (ensure keeps a larger allocation, so
+    // point queries, fans and ray queries share the slot's columns)
+    const size_t full = (size_t)cgrid;
+    const uint32_t ngroups = (uint32_t)((n + rtk::kSegRays - 1) / rtk::kSegRays);
+    const uint32_t grid = (uint32_t)std::min<size_t>(full, (ngroups + 3u) / 4u);
+    if ((rc = ensure(c, L.d_gstack, L.gstack_cap, full * rtk::kBlockThreads * rtk::kGlobalStack))) return rc;
+    if (!L.d_qcnt) {
+        size_t cap = 0;
+        if ((rc = ensure(c, L.d_qcnt, cap, rtk::kCursorSet + 32))) return rc;
+    }
+    for (hipEvent_t& e : L.qev)
+        if (!e) HIPC(c, hipEventCreate(&e));
+    const rtclosest::Scene S{sc.wnodes(), sc.tris(), sc.leaf(), sc.root};
+    const rtclosest::Launch Q{(const float4*)d_pts, (float4*)d_out, (uint32_t)n, L.d_qcnt, L.d_gstack, c->d_overflow};
+    HIPC(c, hipMemsetAsync(L.d_qcnt, 0, (rtk::kCursorSet + 32) * sizeof(uint32_t), s));
+    (void)hipGetLastError();
+    HIPC(c, rtclosest::launch(S, Q, grid, s, L.qev[0], L.qev[1]));
+    HIPC(c, hipEventRecord(L.idle, s));
+    c->query_slot = &L;
+    c->query_last = true;
+    return RT_OK;
+}
+
+int rt_closest_points_device(rt_ctx* c, const rt_point* d_pts, int64_t n, uint32_t flags, rt_closest* d_out, void* stream) {
+    if (const int rc = closest_check(c, "rt_closest_points_device", d_pts, n, flags, d_out)) return rc;
+    if (n == 0) return RT_OK;
+    if (((uintptr_t)d_pts & 15u) || ((uintptr_t)d_out & 15u))
+        return set_err(c, "rt_closest_points_device: d_pts and d_out must be 16-byte aligned", RT_ERR_INVALID_ARG);
+    HIPC(c, hipSetDevice(c->device));
+    return closest_enqueue(c, d_pts, n, d_out, stream ? (hipStream_t)stream : c->stream);
+}
+
+int rt_closest_points(rt_ctx* c, const rt_point* pts, int64_t n, uint32_t flags, rt_closest* out) {
+    if (const int rc = closest_check(c, "rt_closest_points", pts, n, flags, out)) return rc;
+    if (n == 0) return RT_OK;
+    HIPC(c, hipSetDevice(c->device));
+    // pinned, device-mapped caller memory is used directly, anything else is staged: as rt_trace_rays
+    auto mapped = [](const void* p, size_t align) -> void* {
+        hipPointerAttribute_t pa;
+        if (hipPointerGetAttributes(&pa, p) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer &&
+            !((uintptr_t)pa.devicePointer & (align - 1)))
+            return pa.devicePointer;
+        (void)hipGetLastError();   // pageable memory: not an error
+        return nullptr;
+    };
+    const rt_point* d_pts = (const rt_point*)mapped(pts, 16);
+    rt_closest* d_out = (rt_closest*)mapped(out, 16);
+    int rc = RT_OK;
+    if (!d_pts) {   // d_qrays counts 16-B words
+        if ((rc = ensure(c, c->d_qrays, c->qrays_cap, (size_t)n))) return rc;
+        HIPC(c, hipMemcpyAsync(c->d_qrays, pts, (size_t)n * sizeof(rt_point), hipMemcpyHostToDevice, c->stream));
+        d_pts = (const rt_point*)c->d_qrays;
+    }
+    const bool back = !d_out;
+    if (back) {   // d_qhits counts 8-B words
+        if ((rc = ensure(c, c->d_qhits, c->qhits_cap, (size_t)n * (sizeof(rt_closest) / sizeof(uint2))))) return rc;
+        d_out = (rt_closest*)c->d_qhits;
+    }
+    if ((rc = closest_enqueue(c, d_pts, n, d_out, c->stream))) return rc;
+    if (back) HIPC(c, hipMemcpyAsync(out, d_out, (size_t)n * sizeof(rt_closest), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, wait_ctx(c, c->stream));
     return RT_OK;
 }

@@ -82,6 +82,15 @@ class rt_hit(C.Structure):
     _fields_ = [("id", C.c_int32), ("t", C.c_float)]
 
 
+class rt_point(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("r", C.c_float)]
+
+
+class rt_closest(C.Structure):
+    _fields_ = [("id", C.c_int32), ("d2", C.c_float), ("u", C.c_float), ("v", C.c_float),
+                ("px", C.c_float), ("py", C.c_float), ("pz", C.c_float), ("reserved", C.c_uint32)]
+
+
 class rt_hit_attr(C.Structure):
     _fields_ = [("id", C.c_int32), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float),
                 ("px", C.c_float), ("py", C.c_float), ("pz", C.c_float), ("ndotd", C.c_float),
@@ -92,6 +101,9 @@ class rt_hit_attr(C.Structure):
 # the same records as numpy dtypes (trace_rays' and trace_rays_attr's buffers)
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("reserved", np.uint32)])
 HIT_DTYPE = np.dtype([("id", np.int32), ("t", np.float32)])
+POINT_DTYPE = np.dtype([("q", np.float32, 3), ("r", np.float32)])
+CLOSEST_DTYPE = np.dtype([("id", np.int32), ("d2", np.float32), ("u", np.float32), ("v", np.float32),
+                          ("p", np.float32, 3), ("reserved", np.uint32)])
 FAN_ORIGIN_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("n", np.float32, 3), ("reserved", np.uint32)])
 HIT_ATTR_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32),
                            ("p", np.float32, 3), ("ndotd", np.float32),
@@ -134,7 +146,8 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_scene_walk_refs",
                "rt_scene_sah", "rt_trace_rays", "rt_trace_rays_device", "rt_last_query_timing",
                "rt_trace_rays_attr", "rt_trace_rays_attr_device",
-               "rt_trace_fan", "rt_trace_fan_device", "rt_fan_expand"]
+               "rt_trace_fan", "rt_trace_fan_device", "rt_fan_expand",
+               "rt_closest_points", "rt_closest_points_device", "rt_closest_points_host"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
                 "rt_mesh_load_dae", "rt_mesh_save_dae",
                 "rt_mesh_gen_cornell", "rt_mesh_gen_torus_knot", "rt_mesh_gen_heightfield", "rt_mesh_gen_random",
@@ -236,6 +249,9 @@ def lib() -> C.CDLL:
             "rt_trace_fan": (C.c_int, [vp, vp, C.c_int64, vp, i32, u32, vp]),
             "rt_trace_fan_device": (C.c_int, [vp, vp, C.c_int64, vp, i32, u32, vp, vp]),
             "rt_fan_expand": (C.c_int, [vp, C.c_int64, vp, i32, vp, vp]),
+            "rt_closest_points": (C.c_int, [vp, vp, C.c_int64, u32, vp]),
+            "rt_closest_points_device": (C.c_int, [vp, vp, C.c_int64, u32, vp, vp]),
+            "rt_closest_points_host": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, C.c_int64, vp, vp]),
             "rt_bvh_build_lbvh": (C.c_int, [vp, i32, C.POINTER(vp)]),
             "rt_mesh_create": (vp, []),
             "rt_mesh_destroy": (None, [vp]),
@@ -374,6 +390,43 @@ def fan_expand(origins, directions, normals=None, tmax=None):
     traced = np.zeros(n * k, np.uint8)
     _check(lib().rt_fan_expand(_ptr(rec), n, _ptr(d), k, _ptr(rays), _ptr(traced)))
     return rays, traced.astype(bool)
+
+
+def pack_points(points, radius=None) -> np.ndarray:
+    """n rt_point records (POINT_DTYPE) from float32 (n, 3) points and the search radius (None =
+    +inf, a scalar, or float32[n], whose bits are kept: a NaN's payload too)."""
+    q = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    rec = np.zeros(q.shape[0], POINT_DTYPE)
+    rec["q"] = q
+    if radius is None:
+        rec["r"] = np.float32(np.inf)
+    elif np.ndim(radius) == 0:
+        rec["r"] = np.float32(radius)
+    else:
+        r = np.ascontiguousarray(radius, dtype=np.float32).reshape(-1)
+        if r.shape[0] != q.shape[0]:
+            raise ValueError("pack_points: radius has another length than the points")
+        rec["r"].view(np.uint32)[...] = r.view(np.uint32)
+    return rec
+
+
+def closest_points_host(scene: "Scene", points, radius=None, stats: bool = False):
+    """rt_closest_points_host: the definition of Renderer.closest_points in host code, over the
+    scene's arrays (CLOSEST_DTYPE[n]); no GPU.  `points` may be packed POINT_DTYPE records (then the
+    radius is theirs).  stats=True: also {overflows, inner_visits, tri_tests} of the call."""
+    rec = points if getattr(points, "dtype", None) == POINT_DTYPE else pack_points(points, radius)
+    rec = np.ascontiguousarray(rec)
+    v = np.ascontiguousarray(scene.vertices, dtype=np.float32).reshape(-1, 4)
+    idx = np.ascontiguousarray(scene.indices, dtype=np.int32)
+    nodes = np.ascontiguousarray(scene.nodes, dtype=np.float32).reshape(-1, 12)
+    refs = np.ascontiguousarray(scene.tri_indices, dtype=np.int32)
+    out = np.zeros(rec.shape[0], CLOSEST_DTYPE)
+    st = np.zeros(3, np.uint64)
+    _check(lib().rt_closest_points_host(_ptr(v), v.shape[0], _ptr(idx), idx.size, _ptr(nodes), nodes.shape[0], _ptr(refs),
+                                        refs.size, _ptr(rec), rec.shape[0], _ptr(out), _ptr(st) if stats else None))
+    if stats:
+        return out, {"overflows": int(st[0]), "inner_visits": int(st[1]), "tri_tests": int(st[2])}
+    return out
 
 
 def params_to_array(p: rt_params) -> np.ndarray:
@@ -1054,8 +1107,26 @@ class Renderer:
         _check(lib().rt_trace_fan_device(self._h, C.c_void_p(d_origins or None), n, C.c_void_p(d_dirs or None), k, flags,
                                          C.c_void_p(d_masks or None), C.c_void_p(stream or None)), self._h)
 
+    def closest_points(self, points, radius=None) -> np.ndarray:
+        """rt_closest_points: for each of n points the nearest triangle within `radius` (exclusive;
+        None = +inf) -> CLOSEST_DTYPE[n]: id (3 * index; -1: none), squared distance d2, barycentrics
+        (u, v) and the closest point p = (1 - u - v) p0 + u p1 + v p2.  Among equally near triangles
+        the lowest id.  `points` may be packed POINT_DTYPE records (then the radius is theirs)."""
+        rec = points if getattr(points, "dtype", None) == POINT_DTYPE else pack_points(points, radius)
+        rec = np.ascontiguousarray(rec)
+        out = np.zeros(rec.shape[0], CLOSEST_DTYPE)
+        _check(lib().rt_closest_points(self._h, _ptr(rec), rec.shape[0], 0, _ptr(out)), self._h)
+        return out
+
+    def closest_points_device(self, d_pts: int, n: int, d_out: int, flags: int = 0, stream: Optional[int] = None) -> None:
+        """rt_closest_points_device: n rt_point at d_pts -> n rt_closest at d_out (both 16-byte
+        aligned), enqueued on `stream` (None = the ctx's own); returns after enqueue."""
+        _stream_arg(stream)
+        _check(lib().rt_closest_points_device(self._h, C.c_void_p(d_pts or None), n, flags, C.c_void_p(d_out or None),
+                                              C.c_void_p(stream or None)), self._h)
+
     def last_query_ms(self) -> float:
-        """rt_last_query_timing: kernel time of the last ray query of either kind, or fan (ms)."""
+        """rt_last_query_timing: kernel time of the last ray query of either kind, fan or point query (ms)."""
         ms = C.c_float()
         _check(lib().rt_last_query_timing(self._h, C.byref(ms)), self._h)
         return ms.value

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Per-kernel register / scratch / occupancy table of librtamd's device code.
 
-Compiles csrc/rt_render.hip for gfx950 with -Rpass-analysis=kernel-resource-usage (the
-Makefile's `asm` target) and prints one line per kernel: demangled-ish name, VGPRs, AGPRs,
+Compiles csrc/rt_render.hip and csrc/rt_closest.hip for gfx950 with
+-Rpass-analysis=kernel-resource-usage (the Makefile's `asm` target) and prints one line per kernel: demangled-ish name, VGPRs, AGPRs,
 SGPRs, scratch bytes per lane, LDS bytes, waves per SIMD.  Usage:
     python3 scripts/resource_usage.py [filter-substring] [-- extra make args, e.g. KDEFS=-DX=1]
 The filter is a substring of the mangled name: `query_kernel` lists the plain ray query's
 instantiations, `query_attr_kernel` the attribute query's, `query_` both,
-`fan_kernel` the occlusion fan's.
+`fan_kernel` the occlusion fan's, `closest_kernel` the closest-point query's.
 """
 import os
 import re
