@@ -706,6 +706,29 @@ int rt_closest_points_host(const rt_float4* verts, int32_t nv, const int32_t* id
                            const rt_bvh_node* nodes, int32_t nn, const int32_t* refs, int32_t nref,
                            const rt_point* pts, int64_t n, rt_closest* out, uint64_t* stats3);
 
+/* ---- k nearest triangles ----
+ * rt_closest_points with k answers per point: the k nearest DISTINCT triangles within r, ordered by
+ * (d2, id).  out holds k planes of n records: out[j * n + i] is the j-th nearest triangle of point i,
+ * j = 0 the nearest, so plane 0 is rt_closest_points' output; entries beyond the number found are
+ * the miss record.  The records, validity, arithmetic, the radius (exclusive) and the lowest-id rule
+ * are rt_closest_points'; a triangle that the tree references from several leaves appears once.  On
+ * a tree whose boxes contain their triangles plane j is the j-th smallest (d2, id) over ALL triangles
+ * with d2 < r * r, whatever the tree.  An overflow or a malformed inner node makes all k records of the
+ * point a miss; the overflow is counted once.
+ *
+ * flags must be 0.  Refused before any GPU work with RT_ERR_INVALID_ARG: k outside
+ * 1..RT_NEAREST_MAX_K (also with n == 0), n * k > 2^30, and everything rt_closest_points refuses;
+ * RT_ERR_NO_SCENE and n == 0 as there.  Synchrony, the pinned shortcut, streams, the slot,
+ * rt_last_query_timing, rt_last_deferred and rt_overflow_count behave as for rt_closest_points.
+ * rt_nearest_k_host is the definition in host code, as rt_closest_points_host. */
+#define RT_NEAREST_MAX_K 8
+int rt_nearest_k(rt_ctx* ctx, const rt_point* pts, int64_t n, int32_t k, uint32_t flags, rt_closest* out);
+int rt_nearest_k_device(rt_ctx* ctx, const rt_point* d_pts, int64_t n, int32_t k, uint32_t flags,
+                        rt_closest* d_out, void* stream);
+int rt_nearest_k_host(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx,
+                      const rt_bvh_node* nodes, int32_t nn, const int32_t* refs, int32_t nref,
+                      const rt_point* pts, int64_t n, int32_t k, rt_closest* out, uint64_t* stats3);
+
 /* Traversals of the last frame (or of the last ray query, if that came later) that outgrew the
  * fast kernel's LDS stack and restarted in-kernel with the general traversal (same result,
  * slower ray); diagnostics, synchronizes the stream. */

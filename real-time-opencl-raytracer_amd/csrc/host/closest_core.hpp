@@ -1,4 +1,5 @@
-// closest_core.hpp -- the arithmetic and the traversal of a closest-point query that
+// closest_core.hpp -- the arithmetic and the traversal of a closest-point query and of
+// its k-answer form (at the end) that
 // the host twin (closest_points.cpp) and the HIP kernel (rt_closest.hip) share.  Plain inline
 // functions and templates, no HIP types; the kernel compiles them for the device through CLOSEST_HD.
 // Every float operation here is a single IEEE binary32 operation, fmaf only where it is written
@@ -215,6 +216,165 @@ CLOSEST_HD void result_words(const State& T, uint32_t w[8]) {
     c.f = found ? T.p.y : 0.0f;  w[5] = c.u;
     c.f = found ? T.p.z : 0.0f;  w[6] = c.u;
     w[7] = 0u;
+}
+
+// ---- the k nearest triangles ----
+// The traversal above with a list in place of the one answer: L[0 .. K-1], sorted by (d2, id), every
+// entry starting as the sentinel {id = -1, d2 = r * r}.  K is a template parameter so that the list is
+// indexed statically only (registers on the device).  An entry keeps (d2, id, at), `at` the triangle
+// reference record it was found in; u, v and p are tri_point's of that record again at the end.
+constexpr int kMaxK = 8;
+
+template <int K>
+struct StateK {
+    uint32_t cur, nxt;
+    int sc;
+    int tk, tend;
+    float d2[K];
+    int32_t id[K];
+    int32_t at[K];
+    bool overflow;
+    uint64_t inner_visits, tri_tests;   // STATS only
+};
+
+template <int K>
+CLOSEST_HD void start(StateK<K>& T, uint32_t root, float r) {
+    T.cur = root;
+    T.nxt = 0;
+    T.sc = 1;
+    T.tk = T.tend = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        T.d2[j] = r * r;
+        T.id[j] = -1;
+        T.at[j] = 0;
+    }
+    T.overflow = false;
+    T.inner_visits = T.tri_tests = 0;
+}
+
+// all K records a miss (an overflow, or the error reference)
+template <int K>
+CLOSEST_HD void end_as_miss(StateK<K>& T) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) T.id[j] = -1;
+    T.sc = 0;
+}
+
+template <int K, class Stack>
+CLOSEST_HD void pop(StateK<K>& T, const Stack& st) {
+    --T.sc;
+    T.cur = T.nxt;
+    if (T.sc >= 2) T.nxt = st.get(T.sc - 2);
+}
+
+// The candidate (d2, id) of a triangle test.  Presence: an id the list holds is dropped (the SBVH
+// references a triangle from several leaves).  Acceptance: the single answer's rule against the last
+// entry; a NaN is never accepted and r is exclusive.  Insertion: before the first entry the candidate
+// precedes in (d2, id); the entries from there move down one and the last falls off.  A sentinel needs
+// no case of its own: an accepted d2 is strictly below r * r.  An entry that has fallen off and is met
+// again through another reference is refused by acceptance: K entries of the list precede it in the
+// order, and the list only ever moves towards the front of the order.
+template <int K>
+CLOSEST_HD void offer(StateK<K>& T, float d2, int32_t id, int32_t at) {
+    bool present = false;
+#pragma unroll
+    for (int j = 0; j < K; ++j) present = present || T.id[j] == id;
+    if (present) return;
+    if (!(d2 < T.d2[K - 1] || (d2 == T.d2[K - 1] && T.id[K - 1] >= 0 && id < T.id[K - 1]))) return;
+    // before[j]: the candidate precedes entry j; false .. false true .. true along the sorted list
+    bool before[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) before[j] = d2 < T.d2[j] || (d2 == T.d2[j] && id < T.id[j]);
+#pragma unroll
+    for (int j = K - 1; j >= 0; --j) {
+        if (j > 0 && before[j - 1]) {
+            T.d2[j] = T.d2[j - 1];
+            T.id[j] = T.id[j - 1];
+            T.at[j] = T.at[j - 1];
+        } else if (before[j]) {
+            T.d2[j] = d2;
+            T.id[j] = id;
+            T.at[j] = at;
+        }
+    }
+}
+
+// step with the list: the bound is the last entry's d2
+template <bool STATS, int K, class Scene, class Stack>
+CLOSEST_HD void step(StateK<K>& T, const V3& q, const Scene& S, const Stack& st) {
+    if (T.tk >= T.tend && (T.cur & rtrec::kLeafBit)) {
+        int off, cnt;
+        S.leaf(T.cur, off, cnt);
+        if (cnt <= 0) {
+            pop(T, st);
+            return;
+        }
+        T.tk = off;
+        T.tend = off + cnt;
+    }
+    if (T.tk < T.tend) {
+        V3 p0, e1, e2;
+        int32_t id;
+        S.tri(T.tk, p0, e1, e2, id);
+        const TriPoint r = tri_point(q, p0, e1, e2);
+        if (STATS) ++T.tri_tests;
+        offer(T, r.d2, id, (int32_t)T.tk);
+        if (++T.tk == T.tend) {
+            T.tk = T.tend = 0;
+            pop(T, st);
+        }
+        return;
+    }
+    if (T.cur == rtrec::kRefError) {
+        end_as_miss(T);
+        return;
+    }
+    V3 lo0, hi0, lo1, hi1;
+    uint32_t r0, r1;
+    S.inner(T.cur, lo0, hi0, lo1, hi1, r0, r1);
+    if (STATS) ++T.inner_visits;
+    const float b0 = box_d2(q, lo0, hi0), b1 = box_d2(q, lo1, hi1);
+    const bool w0 = box_ordered(lo0, hi0) && b0 <= T.d2[K - 1];   // <=: an equally near lower id is still found
+    const bool w1 = box_ordered(lo1, hi1) && b1 <= T.d2[K - 1];
+    if (w0 && w1) {
+        if (T.sc >= kStackSize) {
+            T.overflow = true;
+            end_as_miss(T);
+            return;
+        }
+        const bool swap = b0 > b1;   // near child first, a tie goes left
+        if (T.sc >= 2) st.put(T.sc - 2, T.nxt);
+        T.nxt = swap ? r0 : r1;
+        T.cur = swap ? r1 : r0;
+        ++T.sc;
+    } else if (w0 || w1) {
+        T.cur = w0 ? r0 : r1;
+    } else {
+        pop(T, st);
+    }
+}
+
+// The 8 words of entry (id, at): tri_point of its triangle reference record again, the words the
+// single answer carries; a miss (id < 0) is {-1, +inf, 0, 0, 0, 0, 0, 0}.
+template <class Scene>
+CLOSEST_HD void entry_words(int32_t eid, int32_t at, const V3& q, const Scene& S, uint32_t w[8]) {
+    union { float f; uint32_t u; } c;
+    w[0] = 0xFFFFFFFFu;
+    c.f = kInf; w[1] = c.u;
+    w[2] = w[3] = w[4] = w[5] = w[6] = w[7] = 0u;
+    if (eid < 0) return;
+    V3 p0, e1, e2;
+    int32_t id;
+    S.tri(at, p0, e1, e2, id);
+    const TriPoint r = tri_point(q, p0, e1, e2);
+    w[0] = (uint32_t)id;
+    c.f = r.d2;  w[1] = c.u;
+    c.f = r.u;   w[2] = c.u;
+    c.f = r.v;   w[3] = c.u;
+    c.f = r.p.x; w[4] = c.u;
+    c.f = r.p.y; w[5] = c.u;
+    c.f = r.p.z; w[6] = c.u;
 }
 
 }  // namespace closest

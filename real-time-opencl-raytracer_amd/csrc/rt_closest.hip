@@ -13,6 +13,7 @@
 //                   definition's, only the interleaving of lanes in time differs.
 //                   The stack is one word per entry: entries 0 .. 15 in the lane's LDS column,
 //                   deeper ones in the lane's global column, [entry][grid lane].
+//   nearest_kernel<K>  rt_nearest_k: the same with a list of K answers, below.
 // One kernel serves every scene: it addresses inner records, triangle records and the escape table
 // by pointer, so split records, malformed nodes and escape leaves need no second instantiation.
 #define CLOSEST_HD __host__ __device__ __forceinline__
@@ -27,6 +28,9 @@
 namespace rtclosest {
 
 namespace {
+
+// waves per SIMD nearest_kernel<K> is bounded to: what its 54 .. 88 VGPRs allow without scratch
+constexpr int nearest_waves(int k) { return k <= 3 ? 8 : k == 4 ? 7 : k <= 6 ? 6 : 5; }
 
 using closest::V3;
 constexpr uint32_t kNoGroup = 0xFFFFFFFFu;
@@ -132,7 +136,63 @@ __global__ void __launch_bounds__(kThreads, RTK_CLOSEST_WAVES) closest_kernel(Sc
     }
 }
 
+// nearest_kernel<K>: rt_nearest_k, closest_kernel with closest_core.hpp's list of K
+// entries in registers in place of the one answer.  An entry is (d2, id, triangle record): at the end a
+// lane evaluates tri_point again for the entries it found and writes plane j of its point to
+// out[j * n + i], every plane as closest_kernel writes its one.  One instantiation per K, so the list
+// is indexed statically only.
+template <int K>
+__global__ void __launch_bounds__(kThreads, nearest_waves(K)) nearest_kernel(Scene Sc, Launch L) {
+    __shared__ uint32_t s_stack[kThreads / 64][kLdsStack][64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t ngroups = (L.n + 63u) / 64u;
+    uint32_t home = blockIdx.x & (kCursors - 1u);
+    const DevScene S{Sc.wnodes, Sc.tris, Sc.leaf_table};
+    DevStack st;
+    st.lds = &s_stack[wave][0][lane];
+    st.glb = L.gstack + ((size_t)blockIdx.x * kThreads + threadIdx.x);
+    st.gstride = (uint64_t)gridDim.x * kThreads;
+    for (;;) {
+        const uint32_t g = grab_group(L.fetch, ngroups, home);
+        if (g == kNoGroup) break;
+        const uint32_t i = g * 64u + lane;
+        const bool inside = i < L.n;
+        float4 pt = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (inside) pt = L.pts[i];
+        closest::StateK<K> T;
+        closest::start(T, Sc.root, pt.w);
+        if (!(inside && closest::point_ok(pt.x, pt.y, pt.z, pt.w))) T.sc = 0;
+        const V3 q{pt.x, pt.y, pt.z};
+        while (T.sc > 0) closest::step<false>(T, q, S, st);
+        if (inside) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                uint32_t w[8];
+                closest::entry_words(T.id[j], T.at[j], q, S, w);
+                float4* o = L.out + ((size_t)j * L.n + i) * 2;
+                o[0] = make_float4(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3]));
+                o[1] = make_float4(__uint_as_float(w[4]), __uint_as_float(w[5]), __uint_as_float(w[6]), __uint_as_float(w[7]));
+            }
+        }
+        if (T.overflow) atomicAdd(L.overflow, 1ull);
+    }
+}
+
+typedef void (*NearestKernel)(Scene, Launch);
+const NearestKernel kNearest[closest::kMaxK] = {nearest_kernel<1>, nearest_kernel<2>, nearest_kernel<3>, nearest_kernel<4>,
+                                                nearest_kernel<5>, nearest_kernel<6>, nearest_kernel<7>, nearest_kernel<8>};
+
 }  // namespace
+
+const void* nearest_kernel_of(int k) { return (const void*)kNearest[k - 1]; }
+
+hipError_t launch_nearest(const Scene& S, const Launch& L, int k, uint32_t grid, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+    Scene sc = S;
+    Launch la = L;
+    void* args[] = {&sc, &la};
+    const hipError_t e = hipExtLaunchKernel((const void*)kNearest[k - 1], dim3(grid), dim3(kThreads), args, 0, s, start, stop, 0);
+    return e != hipSuccess ? e : hipGetLastError();
+}
 
 const void* kernel() { return (const void*)closest_kernel; }
 

@@ -1176,6 +1176,7 @@ struct rt_ctx {
     // the host form's points and records go through d_qrays and d_qhits
     int closest_grid = 0;
     int closest_grid_cap = -1;
+    int nearest_grid[RT_NEAREST_MAX_K] = {};   // rt_nearest_k: the grid of each k's kernel, under the same cap
     FrameSlot* query_slot = nullptr;
     bool query_last = false;
     struct { bool on = false; unsigned long long* d_counts = nullptr; } trace;   // rt_fetch_counts
@@ -3203,8 +3204,9 @@ static int closest_check(rt_ctx* c, const char* who, const void* pts, int64_t n,
     return RT_OK;
 }
 
-// checked arguments, n > 0
-static int closest_enqueue(rt_ctx* c, const rt_point* d_pts, int64_t n, rt_closest* d_out, hipStream_t s) {
+// checked arguments, n > 0.  k == 0: rt_closest_points' kernel and one record per point; k in 1 ..
+// RT_NEAREST_MAX_K: rt_nearest_k's kernel of that k and k planes of n records.
+static int points_enqueue(rt_ctx* c, const rt_point* d_pts, int64_t n, int k, rt_closest* d_out, hipStream_t s) {
     int rc = RT_OK;
     rt_ctx::FrameSlot* Lp = nullptr;
     if ((rc = slot_for(c, (void*)s, kQueryKey, &Lp))) return rc;
@@ -3215,11 +3217,12 @@ static int closest_enqueue(rt_ctx* c, const rt_point* d_pts, int64_t n, rt_close
         const long b = v ? std::strtol(v, nullptr, 10) : 0;
         c->closest_grid_cap = b > 0 && b < (1l << 20) ? (int)b : 0;
     }
-    int& cgrid = c->closest_grid;
+    int& cgrid = k ? c->nearest_grid[k - 1] : c->closest_grid;
     if (!cgrid) {
         int cus = 0, b1 = 0;
         HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, rtclosest::kernel(), rtclosest::kThreads, 0));
+        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, k ? rtclosest::nearest_kernel_of(k) : rtclosest::kernel(),
+                                                             rtclosest::kThreads, 0));
         cgrid = std::max(8, std::max(b1, 1) * cus * RTK_QUERY_GRID_PCT / 100);
         if (c->closest_grid_cap) cgrid = std::min(cgrid, c->closest_grid_cap);
     }
@@ -3239,11 +3242,26 @@ static int closest_enqueue(rt_ctx* c, const rt_point* d_pts, int64_t n, rt_close
     const rtclosest::Launch Q{(const float4*)d_pts, (float4*)d_out, (uint32_t)n, L.d_qcnt, L.d_gstack, c->d_overflow};
     HIPC(c, hipMemsetAsync(L.d_qcnt, 0, (rtk::kCursorSet + 32) * sizeof(uint32_t), s));
     (void)hipGetLastError();
-    HIPC(c, rtclosest::launch(S, Q, grid, s, L.qev[0], L.qev[1]));
+    if (k) HIPC(c, rtclosest::launch_nearest(S, Q, k, grid, s, L.qev[0], L.qev[1]));
+    else HIPC(c, rtclosest::launch(S, Q, grid, s, L.qev[0], L.qev[1]));
     HIPC(c, hipEventRecord(L.idle, s));
     c->query_slot = &L;
     c->query_last = true;
     return RT_OK;
+}
+
+static int closest_enqueue(rt_ctx* c, const rt_point* d_pts, int64_t n, rt_closest* d_out, hipStream_t s) {
+    return points_enqueue(c, d_pts, n, 0, d_out, s);
+}
+
+// pinned, device-mapped caller memory is used directly, anything else is staged: as rt_trace_rays
+static void* mapped_host(const void* p, size_t align) {
+    hipPointerAttribute_t pa;
+    if (hipPointerGetAttributes(&pa, p) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer &&
+        !((uintptr_t)pa.devicePointer & (align - 1)))
+        return pa.devicePointer;
+    (void)hipGetLastError();   // pageable memory: not an error
+    return nullptr;
 }
 
 int rt_closest_points_device(rt_ctx* c, const rt_point* d_pts, int64_t n, uint32_t flags, rt_closest* d_out, void* stream) {
@@ -3259,17 +3277,8 @@ int rt_closest_points(rt_ctx* c, const rt_point* pts, int64_t n, uint32_t flags,
     if (const int rc = closest_check(c, "rt_closest_points", pts, n, flags, out)) return rc;
     if (n == 0) return RT_OK;
     HIPC(c, hipSetDevice(c->device));
-    // pinned, device-mapped caller memory is used directly, anything else is staged: as rt_trace_rays
-    auto mapped = [](const void* p, size_t align) -> void* {
-        hipPointerAttribute_t pa;
-        if (hipPointerGetAttributes(&pa, p) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer &&
-            !((uintptr_t)pa.devicePointer & (align - 1)))
-            return pa.devicePointer;
-        (void)hipGetLastError();   // pageable memory: not an error
-        return nullptr;
-    };
-    const rt_point* d_pts = (const rt_point*)mapped(pts, 16);
-    rt_closest* d_out = (rt_closest*)mapped(out, 16);
+    const rt_point* d_pts = (const rt_point*)mapped_host(pts, 16);
+    rt_closest* d_out = (rt_closest*)mapped_host(out, 16);
     int rc = RT_OK;
     if (!d_pts) {   // d_qrays counts 16-B words
         if ((rc = ensure(c, c->d_qrays, c->qrays_cap, (size_t)n))) return rc;
@@ -3283,6 +3292,53 @@ int rt_closest_points(rt_ctx* c, const rt_point* pts, int64_t n, uint32_t flags,
     }
     if ((rc = closest_enqueue(c, d_pts, n, d_out, c->stream))) return rc;
     if (back) HIPC(c, hipMemcpyAsync(out, d_out, (size_t)n * sizeof(rt_closest), hipMemcpyDeviceToHost, c->stream));
+    HIPC(c, wait_ctx(c, c->stream));
+    return RT_OK;
+}
+
+// ---- k nearest triangles ----
+// rt_closest_points with k records per point, in k planes of n: the same slot, grid rule, staging and
+// events; the kernel is rt_closest.hip's nearest_kernel<k>.
+static int nearest_check(rt_ctx* c, const char* who, const void* pts, int64_t n, int32_t k, uint32_t flags, const void* out) {
+    if (const int rc = closest_check(c, who, pts, n, flags, out)) return rc;
+    if (k < 1 || k > RT_NEAREST_MAX_K) return set_err(c, std::string(who) + ": k must be 1..8", RT_ERR_INVALID_ARG);
+    if (n * k > kMaxQueryRays) return set_err(c, std::string(who) + ": n * k must be at most 2^30", RT_ERR_INVALID_ARG);
+    return RT_OK;
+}
+
+static int nearest_enqueue(rt_ctx* c, const rt_point* d_pts, int64_t n, int32_t k, rt_closest* d_out, hipStream_t s) {
+    return points_enqueue(c, d_pts, n, k, d_out, s);
+}
+
+int rt_nearest_k_device(rt_ctx* c, const rt_point* d_pts, int64_t n, int32_t k, uint32_t flags, rt_closest* d_out, void* stream) {
+    if (const int rc = nearest_check(c, "rt_nearest_k_device", d_pts, n, k, flags, d_out)) return rc;
+    if (n == 0) return RT_OK;
+    if (((uintptr_t)d_pts & 15u) || ((uintptr_t)d_out & 15u))
+        return set_err(c, "rt_nearest_k_device: d_pts and d_out must be 16-byte aligned", RT_ERR_INVALID_ARG);
+    HIPC(c, hipSetDevice(c->device));
+    return nearest_enqueue(c, d_pts, n, k, d_out, stream ? (hipStream_t)stream : c->stream);
+}
+
+int rt_nearest_k(rt_ctx* c, const rt_point* pts, int64_t n, int32_t k, uint32_t flags, rt_closest* out) {
+    if (const int rc = nearest_check(c, "rt_nearest_k", pts, n, k, flags, out)) return rc;
+    if (n == 0) return RT_OK;
+    HIPC(c, hipSetDevice(c->device));
+    const rt_point* d_pts = (const rt_point*)mapped_host(pts, 16);
+    rt_closest* d_out = (rt_closest*)mapped_host(out, 16);
+    int rc = RT_OK;
+    if (!d_pts) {   // d_qrays counts 16-B words
+        if ((rc = ensure(c, c->d_qrays, c->qrays_cap, (size_t)n))) return rc;
+        HIPC(c, hipMemcpyAsync(c->d_qrays, pts, (size_t)n * sizeof(rt_point), hipMemcpyHostToDevice, c->stream));
+        d_pts = (const rt_point*)c->d_qrays;
+    }
+    const size_t nrec = (size_t)n * (size_t)k;
+    const bool back = !d_out;
+    if (back) {   // d_qhits counts 8-B words
+        if ((rc = ensure(c, c->d_qhits, c->qhits_cap, nrec * (sizeof(rt_closest) / sizeof(uint2))))) return rc;
+        d_out = (rt_closest*)c->d_qhits;
+    }
+    if ((rc = nearest_enqueue(c, d_pts, n, k, d_out, c->stream))) return rc;
+    if (back) HIPC(c, hipMemcpyAsync(out, d_out, nrec * sizeof(rt_closest), hipMemcpyDeviceToHost, c->stream));
     HIPC(c, wait_ctx(c, c->stream));
     return RT_OK;
 }

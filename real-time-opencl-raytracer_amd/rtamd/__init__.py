@@ -147,7 +147,8 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_scene_sah", "rt_trace_rays", "rt_trace_rays_device", "rt_last_query_timing",
                "rt_trace_rays_attr", "rt_trace_rays_attr_device",
                "rt_trace_fan", "rt_trace_fan_device", "rt_fan_expand",
-               "rt_closest_points", "rt_closest_points_device", "rt_closest_points_host"]
+               "rt_closest_points", "rt_closest_points_device", "rt_closest_points_host",
+               "rt_nearest_k", "rt_nearest_k_device", "rt_nearest_k_host"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
                 "rt_mesh_load_dae", "rt_mesh_save_dae",
                 "rt_mesh_gen_cornell", "rt_mesh_gen_torus_knot", "rt_mesh_gen_heightfield", "rt_mesh_gen_random",
@@ -252,6 +253,9 @@ def lib() -> C.CDLL:
             "rt_closest_points": (C.c_int, [vp, vp, C.c_int64, u32, vp]),
             "rt_closest_points_device": (C.c_int, [vp, vp, C.c_int64, u32, vp, vp]),
             "rt_closest_points_host": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, C.c_int64, vp, vp]),
+            "rt_nearest_k": (C.c_int, [vp, vp, C.c_int64, i32, u32, vp]),
+            "rt_nearest_k_device": (C.c_int, [vp, vp, C.c_int64, i32, u32, vp, vp]),
+            "rt_nearest_k_host": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, C.c_int64, i32, vp, vp]),
             "rt_bvh_build_lbvh": (C.c_int, [vp, i32, C.POINTER(vp)]),
             "rt_mesh_create": (vp, []),
             "rt_mesh_destroy": (None, [vp]),
@@ -424,6 +428,25 @@ def closest_points_host(scene: "Scene", points, radius=None, stats: bool = False
     st = np.zeros(3, np.uint64)
     _check(lib().rt_closest_points_host(_ptr(v), v.shape[0], _ptr(idx), idx.size, _ptr(nodes), nodes.shape[0], _ptr(refs),
                                         refs.size, _ptr(rec), rec.shape[0], _ptr(out), _ptr(st) if stats else None))
+    if stats:
+        return out, {"overflows": int(st[0]), "inner_visits": int(st[1]), "tri_tests": int(st[2])}
+    return out
+
+
+def nearest_k_host(scene: "Scene", points, k: int, r=None, stats: bool = False):
+    """rt_nearest_k_host: the definition of Renderer.nearest_k in host code, over the scene's arrays
+    (CLOSEST_DTYPE (k, n)); no GPU.  `points` may be packed POINT_DTYPE records (then the radius is
+    theirs).  stats=True: also {overflows, inner_visits, tri_tests} of the call."""
+    rec = points if getattr(points, "dtype", None) == POINT_DTYPE else pack_points(points, r)
+    rec = np.ascontiguousarray(rec)
+    v = np.ascontiguousarray(scene.vertices, dtype=np.float32).reshape(-1, 4)
+    idx = np.ascontiguousarray(scene.indices, dtype=np.int32)
+    nodes = np.ascontiguousarray(scene.nodes, dtype=np.float32).reshape(-1, 12)
+    refs = np.ascontiguousarray(scene.tri_indices, dtype=np.int32)
+    out = np.zeros((max(int(k), 0), rec.shape[0]), CLOSEST_DTYPE)
+    st = np.zeros(3, np.uint64)
+    _check(lib().rt_nearest_k_host(_ptr(v), v.shape[0], _ptr(idx), idx.size, _ptr(nodes), nodes.shape[0], _ptr(refs),
+                                   refs.size, _ptr(rec), rec.shape[0], k, _ptr(out), _ptr(st) if stats else None))
     if stats:
         return out, {"overflows": int(st[0]), "inner_visits": int(st[1]), "tri_tests": int(st[2])}
     return out
@@ -1124,6 +1147,24 @@ class Renderer:
         _stream_arg(stream)
         _check(lib().rt_closest_points_device(self._h, C.c_void_p(d_pts or None), n, flags, C.c_void_p(d_out or None),
                                               C.c_void_p(stream or None)), self._h)
+
+    def nearest_k(self, points, k: int, r=None) -> np.ndarray:
+        """rt_nearest_k: for each of n points the k (1..8) nearest distinct triangles within `r`
+        (exclusive; None = +inf) -> CLOSEST_DTYPE (k, n), row j the j-th nearest of every point, ordered
+        by (d2, id); entries beyond the number found are the miss record (id -1, d2 +inf).  Row 0 is
+        closest_points' result.  `points` may be packed POINT_DTYPE records (then the radius is theirs)."""
+        rec = points if getattr(points, "dtype", None) == POINT_DTYPE else pack_points(points, r)
+        rec = np.ascontiguousarray(rec)
+        out = np.zeros((max(int(k), 0), rec.shape[0]), CLOSEST_DTYPE)
+        _check(lib().rt_nearest_k(self._h, _ptr(rec), rec.shape[0], k, 0, _ptr(out)), self._h)
+        return out
+
+    def nearest_k_device(self, d_pts: int, n: int, k: int, d_out: int, flags: int = 0, stream: Optional[int] = None) -> None:
+        """rt_nearest_k_device: n rt_point at d_pts -> k planes of n rt_closest at d_out (both 16-byte
+        aligned), enqueued on `stream` (None = the ctx's own); returns after enqueue."""
+        _stream_arg(stream)
+        _check(lib().rt_nearest_k_device(self._h, C.c_void_p(d_pts or None), n, k, flags, C.c_void_p(d_out or None),
+                                         C.c_void_p(stream or None)), self._h)
 
     def last_query_ms(self) -> float:
         """rt_last_query_timing: kernel time of the last ray query of either kind, fan or point query (ms)."""
