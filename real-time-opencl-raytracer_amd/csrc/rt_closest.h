@@ -28,16 +28,15 @@ struct Launch {
     unsigned long long* overflow;
 };
 
+// k == 0: rt_closest_points' kernel, one record per point.  k in 1 .. 8: rt_nearest_k's kernel of that k
+// (DESIGN.md 23), the k nearest triangles per point; L.out then holds k planes of L.n records, plane j
+// at out + j * n.
+
 // the kernel, for the occupancy query that sizes the persistent grid
-const void* kernel();
+const void* kernel(int k);
 
 // Enqueues the kernel on `s` with `grid` blocks; start / stop as hipExtLaunchKernel takes them.
 // Read-only on the scene.  n > 0, grid > 0.
-hipError_t launch(const Scene& S, const Launch& L, uint32_t grid, hipStream_t s, hipEvent_t start, hipEvent_t stop);
-
-// rt_nearest_k: the k nearest triangles per point, k in 1 .. 8.  L.out holds k planes of
-// L.n records, plane j at out + j * n; everything else is launch()'s.  One kernel per k.
-const void* nearest_kernel_of(int k);
-hipError_t launch_nearest(const Scene& S, const Launch& L, int k, uint32_t grid, hipStream_t s, hipEvent_t start, hipEvent_t stop);
+hipError_t launch(const Scene& S, const Launch& L, int k, uint32_t grid, hipStream_t s, hipEvent_t start, hipEvent_t stop);
 
 }  // namespace rtclosest

@@ -184,23 +184,13 @@ const NearestKernel kNearest[closest::kMaxK] = {nearest_kernel<1>, nearest_kerne
 
 }  // namespace
 
-const void* nearest_kernel_of(int k) { return (const void*)kNearest[k - 1]; }
+const void* kernel(int k) { return k ? (const void*)kNearest[k - 1] : (const void*)closest_kernel; }
 
-hipError_t launch_nearest(const Scene& S, const Launch& L, int k, uint32_t grid, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+hipError_t launch(const Scene& S, const Launch& L, int k, uint32_t grid, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     Scene sc = S;
     Launch la = L;
     void* args[] = {&sc, &la};
-    const hipError_t e = hipExtLaunchKernel((const void*)kNearest[k - 1], dim3(grid), dim3(kThreads), args, 0, s, start, stop, 0);
-    return e != hipSuccess ? e : hipGetLastError();
-}
-
-const void* kernel() { return (const void*)closest_kernel; }
-
-hipError_t launch(const Scene& S, const Launch& L, uint32_t grid, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
-    Scene sc = S;
-    Launch la = L;
-    void* args[] = {&sc, &la};
-    const hipError_t e = hipExtLaunchKernel((const void*)closest_kernel, dim3(grid), dim3(kThreads), args, 0, s, start, stop, 0);
+    const hipError_t e = hipExtLaunchKernel(kernel(k), dim3(grid), dim3(kThreads), args, 0, s, start, stop, 0);
     return e != hipSuccess ? e : hipGetLastError();
 }
 

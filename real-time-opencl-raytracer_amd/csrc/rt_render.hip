@@ -1162,21 +1162,22 @@ struct rt_ctx {
     std::vector<OrderTab> orders;
     uint32_t scene_gen = 0;                                   // bumped by every upload
     int wf_grid[3] = {0, 0, 0};   // persistent wavefront grid per math mode
-    // ray queries: the persistent grid per math mode, the host form's staging, and the
-    // slot of the last query while no frame has come after it (rt_last_deferred, rt_last_query_timing)
-    int query_grid[2][3] = {{0, 0, 0}, {0, 0, 0}};   // [record kind][math]
-    float4* d_qrays = nullptr; size_t qrays_cap = 0;
-    uint2* d_qhits = nullptr; size_t qhits_cap = 0;
-    // occlusion fans: the persistent grid per math mode, the host form's direction table
-    // (its origins and masks go through d_qrays and d_qhits), RTAMD_FAN_GRID_BLOCKS (-1: not read yet)
-    int fan_grid[3] = {0, 0, 0};
-    float4* d_fdirs = nullptr; size_t fdirs_cap = 0;
-    int fan_grid_cap = -1;
-    // closest-point queries: the persistent grid, RTAMD_CLOSEST_GRID_BLOCKS (-1: not read yet);
-    // the host form's points and records go through d_qrays and d_qhits
-    int closest_grid = 0;
-    int closest_grid_cap = -1;
-    int nearest_grid[RT_NEAREST_MAX_K] = {};   // rt_nearest_k: the grid of each k's kernel, under the same cap
+    // The query families launch through query_launch, which fills these on first use:
+    // the persistent grid of each kernel (0: not computed yet) and the test cap of the families that
+    // have one (grid_cap; -1: not read yet)
+    int query_grid[2][3] = {{0, 0, 0}, {0, 0, 0}};   // ray queries: [record kind][math]
+    int fan_grid[3] = {0, 0, 0};                     // fans: [math]
+    int fan_grid_cap = -1;                           //   RTAMD_FAN_GRID_BLOCKS
+    int closest_grid = 0;                            // rt_closest_points
+    int nearest_grid[RT_NEAREST_MAX_K] = {};         // rt_nearest_k: [k - 1]
+    int closest_grid_cap = -1;                       //   RTAMD_CLOSEST_GRID_BLOCKS, both point families
+    // The host forms' staging (stage_in, stage_dst, stage_out), shared by every family, grow-only,
+    // capacities in bytes: d_qrays takes the rays, fan origins or points, d_fdirs a fan's direction
+    // table, d_qhits gives the hits, masks or records back
+    char* d_qrays = nullptr; size_t qrays_cap = 0;
+    char* d_qhits = nullptr; size_t qhits_cap = 0;
+    char* d_fdirs = nullptr; size_t fdirs_cap = 0;
+    // the slot of the last query while no frame has come after it (rt_last_deferred, rt_last_query_timing)
     FrameSlot* query_slot = nullptr;
     bool query_last = false;
     struct { bool on = false; unsigned long long* d_counts = nullptr; } trace;   // rt_fetch_counts
@@ -2359,6 +2360,23 @@ int64_t rt_tiling_pixels(uint32_t w, uint32_t h, const rt_tiling* t) {
     return rows * w;
 }
 
+// The scene as every frame and query kernel takes it.  flags: RT_FLAG_EXACT_DIV keeps the slab test's division.
+static rtk::DevScene dev_scene(const Scene& sc, uint32_t flags) {
+    return rtk::DevScene{sc.wnodes(),
+                         sc.tris(),
+                         sc.shade(),
+                         sc.leaf(),
+                         (uint32_t)(sc.n_wnodes4 * 16),
+                         (uint32_t)(sc.rec_units() * 16),
+                         sc.root,
+                         sc.n_inner,
+                         (sc.fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,
+                         sc.clean};
+}
+// the fast kernels (any quotient domain: traverse_fast picks the variant) need a clean scene
+// whose records one buffer descriptor covers; frames and queries alike
+static bool scene_fast(const Scene& sc) { return sc.clean != 0 && !sc.split; }
+
 // rt_render_device, and (batch != null) rt_render_device_batch: nbatch depth-1 frames with the
 // cameras batch[0..nbatch-1] in one launch, frame i at d_out + i * bstride
 static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint32_t flags, const rt_tiling* tiling,
@@ -2444,16 +2462,7 @@ static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint3
     F.num_blocks = F.tiles_x * F.tiles_y;
 
     const Scene& sc = c->scene;
-    rtk::DevScene S{sc.wnodes(),
-                    sc.tris(),
-                    sc.shade(),
-                    sc.leaf(),
-                    (uint32_t)(sc.n_wnodes4 * 16),
-                    (uint32_t)(sc.rec_units() * 16),
-                    sc.root,
-                    sc.n_inner,
-                    (sc.fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,
-                    sc.clean};
+    rtk::DevScene S = dev_scene(sc, flags);
     rtk::Outputs O;
     O.out = d_out;
     O.hits = aux ? d_aux->hits : nullptr;
@@ -2567,9 +2576,7 @@ static int render_frames(rt_ctx* c, uint32_t w, uint32_t h, int32_t depth, uint3
             F.done = L.d_done;
         }
     }
-    // the fast kernels (any quotient domain: traverse_fast picks the variant) need a clean scene
-    // whose records one buffer descriptor covers
-    const bool fast = S.clean != 0 && !sc.split;
+    const bool fast = scene_fast(sc);
     // The depth-1 kernels walk by the scene's walk references.  A scene without them (a leaf of more
     // than 16 references: only an uploaded foreign BVH has one) renders its depth-1 frames with the
     // general traversal, as an unclean scene does: same pixels.
@@ -2900,27 +2907,137 @@ int rt_timing_average(rt_ctx* c, int32_t n, float* total_ms, float* traverse_ms)
     return RT_OK;
 }
 
-// ---- ray queries (DESIGN.md 18) ----
-// A query takes a frame slot of its own kind per stream (kQueryKey: no tiling has that key), so
-// install_scene and update_vertices wait for it through the slot's idle event as they do for frames,
-// and queries on different streams may run concurrently.  The slot holds the spill stack (one
-// column per lane of the persistent grid, sized once: the grid is the context's), the launch's
-// work cursors and restart count (zeroed on the stream before every launch) and the two events
-// around the kernel.
+}  // extern "C": the families' shared path has templates
+
+// ---- the query families: ray queries, fans, closest points, k nearest ----
+// Every family launches through query_launch and is a query to everything that waits for or
+// reports on one.  A query takes a frame slot of its own kind per stream (kQueryKey: no tiling has
+// that key), so install_scene and update_vertices wait for it through the slot's idle event as they
+// do for frames, and queries on different streams may run concurrently.  The slot holds the spill
+// stack (one column per lane of the persistent grid, sized once: the grid is the context's), the
+// launch's work cursors and restart count (zeroed on the stream before every launch) and the two
+// events around the kernel.  A family brings its checks (over check_count and check_flags_scene),
+// its kernel arguments and its launch; the host forms stage through stage_in, stage_dst and stage_out.
 constexpr uint64_t kQueryKey = 1ull << 62;
 constexpr int64_t kMaxQueryRays = 1ll << 30;
 constexpr uint32_t kQueryFlags = RT_FLAG_HW_MATH | RT_FLAG_STRICT_MATH | RT_FLAG_EXACT_DIV | RT_FLAG_ANY_HIT;
 
-// the refusals that need no GPU; `who` names the entry point in the message
-static int query_check(rt_ctx* c, const char* who, const void* rays, int64_t n, uint32_t flags, const void* hits) {
+// The refusals that need no GPU, `who` naming the entry point in the message, are every family's in
+// this order: check_count, the family's own (NULL pointers; before them a fan's k), check_flags_scene.
+static int check_count(rt_ctx* c, const char* who, int64_t n, int64_t n_max, const char* range) {
     if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
-    if (n < 0 || n > kMaxQueryRays) return set_err(c, std::string(who) + ": n must be 0..2^30", RT_ERR_INVALID_ARG);
-    if (n > 0 && (!rays || !hits)) return set_err(c, std::string(who) + ": rays or hits is NULL", RT_ERR_INVALID_ARG);
-    if (flags & ~kQueryFlags) return set_err(c, std::string(who) + ": a flag that is not a ray query's", RT_ERR_INVALID_ARG);
+    if (n < 0 || n > n_max) return set_err(c, std::string(who) + ": n must be " + range, RT_ERR_INVALID_ARG);
+    return RT_OK;
+}
+static int check_flags_scene(rt_ctx* c, const char* who, uint32_t flags, uint32_t mask, const char* not_ours) {
+    if (flags & ~mask) return set_err(c, std::string(who) + not_ours, RT_ERR_INVALID_ARG);
     if ((flags & RT_FLAG_STRICT_MATH) && (flags & RT_FLAG_HW_MATH))
         return set_err(c, std::string(who) + ": RT_FLAG_STRICT_MATH and RT_FLAG_HW_MATH exclude each other", RT_ERR_INVALID_ARG);
     if (!c->have_scene) return set_err(c, std::string(who) + ": no scene uploaded", RT_ERR_NO_SCENE);
     return RT_OK;
+}
+
+// RTAMD_FAN_GRID_BLOCKS, RTAMD_CLOSEST_GRID_BLOCKS = <b> (tests): at most b blocks in the family's grids,
+// so that a wave takes many items.  Read once per context (memo -1: not read yet); 0: no cap.
+static int grid_cap(const char* var, int& memo) {
+    if (memo < 0) {
+        const char* v = std::getenv(var);
+        const long b = v ? std::strtol(v, nullptr, 10) : 0;
+        memo = b > 0 && b < (1l << 20) ? (int)b : 0;
+    }
+    return memo;
+}
+
+// One query on `s`, checked arguments.  `grid_memo` is the context's cell for the persistent grid of
+// `kernel` (the family's kernel whose occupancy sizes it): computed once, under `cap` blocks if that
+// is not 0.  `items` is what the launch's waves take one at a time, four waves to a block.
+// launch(slot, grid) enqueues the kernel between the slot's events, on zeroed cursors.
+template <class Launch>
+static int query_launch(rt_ctx* c, hipStream_t s, int& grid_memo, const void* kernel, int cap, uint32_t items, Launch launch) {
+    int rc = RT_OK;
+    rt_ctx::FrameSlot* Lp = nullptr;
+    if ((rc = slot_for(c, (void*)s, kQueryKey, &Lp))) return rc;
+    rt_ctx::FrameSlot& L = *Lp;
+    if (!grid_memo) {
+        int cus = 0, b1 = 0;
+        HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, kernel, rtk::kBlockThreads, 0));
+        grid_memo = std::max(8, std::max(b1, 1) * cus * RTK_QUERY_GRID_PCT / 100);
+        if (cap) grid_memo = std::min(grid_memo, cap);
+    }
+    // the stack columns are sized for the kernel's whole grid, whatever the launch takes: a later, larger
+    // query allocates nothing (ensure keeps a larger allocation, so the families share the slot's columns)
+    const size_t full = (size_t)grid_memo;
+    const uint32_t grid = (uint32_t)std::min<size_t>(full, (items + 3u) / 4u);
+    if ((rc = ensure(c, L.d_gstack, L.gstack_cap, full * rtk::kBlockThreads * rtk::kGlobalStack))) return rc;
+    if (!L.d_qcnt) {
+        size_t qcnt_cap = 0;
+        if ((rc = ensure(c, L.d_qcnt, qcnt_cap, rtk::kCursorSet + 32))) return rc;
+    }
+    for (hipEvent_t& e : L.qev)
+        if (!e) HIPC(c, hipEventCreate(&e));
+    HIPC(c, hipMemsetAsync(L.d_qcnt, 0, (rtk::kCursorSet + 32) * sizeof(uint32_t), s));
+    (void)hipGetLastError();
+    HIPC(c, launch(L, grid));
+    HIPC(c, hipGetLastError());
+    HIPC(c, hipEventRecord(L.idle, s));
+    c->query_slot = &L;
+    c->query_last = true;
+    return RT_OK;
+}
+
+// what the render kernels' body writes besides a query's records: the spill stack, its stride, the counters
+static rtk::Outputs query_outputs(rt_ctx* c, const rt_ctx::FrameSlot& L, uint32_t grid) {
+    rtk::Outputs O{};
+    O.gstack = L.d_gstack;
+    O.overflow = c->d_overflow;
+    O.restarts = L.d_qcnt + rtk::kCursorSet;
+    O.local_pixels = (uint64_t)grid * rtk::kBlockThreads;   // the stack's stride: the lanes launched
+    return O;
+}
+
+// Pinned host memory that the device can reach (hipHostMalloc, or registered as mapped) at an
+// address aligned to `align`: that address, which a host form then uses directly, as rt_render does.
+static void* mapped_host(const void* p, size_t align) {
+    hipPointerAttribute_t pa;
+    if (hipPointerGetAttributes(&pa, p) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer &&
+        !((uintptr_t)pa.devicePointer & (align - 1)))
+        return pa.devicePointer;
+    (void)hipGetLastError();   // pageable memory: not an error
+    return nullptr;
+}
+
+// A host form's input of `bytes` bytes -> *dev: the caller's memory where mapped_host gives it, else a
+// copy made on c->stream in the staging buffer `buf` (grow-only, `cap` in bytes)
+template <class T>
+static int stage_in(rt_ctx* c, const T* host, size_t bytes, size_t align, char*& buf, size_t& cap, const T** dev) {
+    if ((*dev = (const T*)mapped_host(host, align))) return RT_OK;
+    if (const int rc = ensure(c, buf, cap, bytes)) return rc;
+    HIPC(c, hipMemcpyAsync(buf, host, bytes, hipMemcpyHostToDevice, c->stream));
+    *dev = (const T*)buf;
+    return RT_OK;
+}
+// A host form's output of `bytes` bytes -> *dev: the caller's memory where mapped_host gives it, else
+// d_qhits, which stage_out copies back on c->stream after the query (and nothing where nothing was staged)
+template <class T>
+static int stage_dst(rt_ctx* c, T* host, size_t bytes, size_t align, T** dev) {
+    if ((*dev = (T*)mapped_host(host, align))) return RT_OK;
+    if (const int rc = ensure(c, c->d_qhits, c->qhits_cap, bytes)) return rc;
+    *dev = (T*)c->d_qhits;
+    return RT_OK;
+}
+static int stage_out(rt_ctx* c, void* host, const void* dev, size_t bytes) {
+    if (dev == c->d_qhits) HIPC(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    return RT_OK;
+}
+
+extern "C" {
+
+// ---- ray queries (DESIGN.md 18) ----
+static int query_check(rt_ctx* c, const char* who, const void* rays, int64_t n, uint32_t flags, const void* hits) {
+    if (const int rc = check_count(c, who, n, kMaxQueryRays, "0..2^30")) return rc;
+    if (n > 0 && (!rays || !hits)) return set_err(c, std::string(who) + ": rays or hits is NULL", RT_ERR_INVALID_ARG);
+    return check_flags_scene(c, who, flags, kQueryFlags, ": a flag that is not a ray query's");
 }
 
 // A query's record kind: rt_hit (query_kernel) or rt_hit_attr (query_attr_kernel).  Both
@@ -2932,59 +3049,18 @@ static void* kernel_query_of(QueryKind kind, int m, bool any, bool fast) {
 
 // checked arguments, n > 0; d_hits: rt_hit[n] or rt_hit_attr[n], by kind
 static int query_enqueue(rt_ctx* c, QueryKind kind, const rt_ray* d_rays, int64_t n, uint32_t flags, void* d_hits, hipStream_t s) {
-    int rc = RT_OK;
-    rt_ctx::FrameSlot* Lp = nullptr;
-    if ((rc = slot_for(c, (void*)s, kQueryKey, &Lp))) return rc;
-    rt_ctx::FrameSlot& L = *Lp;
     const int math = (flags & RT_FLAG_STRICT_MATH) ? 0 : (flags & RT_FLAG_HW_MATH) ? 1 : 2;
     const bool any = (flags & RT_FLAG_ANY_HIT) != 0;
-    const Scene& sc = c->scene;
-    rtk::DevScene S{sc.wnodes(),
-                    sc.tris(),
-                    sc.shade(),
-                    sc.leaf(),
-                    (uint32_t)(sc.n_wnodes4 * 16),
-                    (uint32_t)(sc.rec_units() * 16),
-                    sc.root,
-                    sc.n_inner,
-                    (sc.fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,
-                    sc.clean};
-    const bool fast = S.clean != 0 && !sc.split;   // as for frames (render_frames)
-    int& qgrid = c->query_grid[kind][math];
-    if (!qgrid) {
-        int cus = 0, b1 = 0;
-        HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, (const void*)kernel_query_of(kind, math, false, true), 256, 0));
-        qgrid = std::max(8, std::max(b1, 1) * cus * RTK_QUERY_GRID_PCT / 100);
-    }
-    // the stack columns are sized for the mode's whole grid, whatever n is: a later, larger query allocates nothing
-    // (ensure keeps a larger allocation, so the two kinds share the slot's columns)
-    const size_t full = (size_t)qgrid;
+    rtk::DevScene S = dev_scene(c->scene, flags);
+    void* kernel = kernel_query_of(kind, math, any, scene_fast(c->scene));
     const uint32_t ngroups = (uint32_t)((n + rtk::kSegRays - 1) / rtk::kSegRays);
-    const uint32_t grid = (uint32_t)std::min<size_t>(full, (ngroups + 3u) / 4u);
-    if ((rc = ensure(c, L.d_gstack, L.gstack_cap, full * rtk::kBlockThreads * rtk::kGlobalStack))) return rc;
-    if (!L.d_qcnt) {
-        size_t cap = 0;
-        if ((rc = ensure(c, L.d_qcnt, cap, rtk::kCursorSet + 32))) return rc;
-    }
-    for (hipEvent_t& e : L.qev)
-        if (!e) HIPC(c, hipEventCreate(&e));
-    rtk::Outputs O{};
-    O.gstack = L.d_gstack;
-    O.overflow = c->d_overflow;
-    O.restarts = L.d_qcnt + rtk::kCursorSet;
-    O.local_pixels = (uint64_t)grid * rtk::kBlockThreads;   // the stack's stride: the lanes launched
-    rtk::Query Q{(const float4*)d_rays, (uint2*)d_hits, (uint32_t)n, L.d_qcnt};
-    HIPC(c, hipMemsetAsync(L.d_qcnt, 0, (rtk::kCursorSet + 32) * sizeof(uint32_t), s));
-    (void)hipGetLastError();
-    void* args[] = {&S, &O, &Q};
-    HIPC(c, hipExtLaunchKernel(kernel_query_of(kind, math, any, fast), dim3(grid), dim3(rtk::kBlockThreads), args, 0, s, L.qev[0],
-                               L.qev[1], 0));
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(L.idle, s));
-    c->query_slot = &L;
-    c->query_last = true;
-    return RT_OK;
+    return query_launch(c, s, c->query_grid[kind][math], kernel_query_of(kind, math, false, true), 0, ngroups,
+                        [&](rt_ctx::FrameSlot& L, uint32_t grid) {
+                            rtk::Outputs O = query_outputs(c, L, grid);
+                            rtk::Query Q{(const float4*)d_rays, (uint2*)d_hits, (uint32_t)n, L.d_qcnt};
+                            void* args[] = {&S, &O, &Q};
+                            return hipExtLaunchKernel(kernel, dim3(grid), dim3(rtk::kBlockThreads), args, 0, s, L.qev[0], L.qev[1], 0);
+                        });
 }
 
 // the two entry points of either record kind; `who` names the caller's
@@ -3005,32 +3081,14 @@ static int trace_rays_host(rt_ctx* c, QueryKind kind, const char* who, const rt_
     if (const int rc = query_check(c, who, rays, n, flags, hits)) return rc;
     if (n == 0) return RT_OK;
     HIPC(c, hipSetDevice(c->device));
-    // pinned host memory the device can reach (hipHostMalloc, or registered as mapped) is used
-    // directly, as by rt_render; anything else goes through the context's staging
-    auto mapped = [](const void* p, size_t align) -> void* {
-        hipPointerAttribute_t pa;
-        if (hipPointerGetAttributes(&pa, p) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer &&
-            !((uintptr_t)pa.devicePointer & (align - 1)))
-            return pa.devicePointer;
-        (void)hipGetLastError();   // pageable memory: not an error
-        return nullptr;
-    };
-    const size_t rec = kind == kQueryAttr ? sizeof(rt_hit_attr) : sizeof(rt_hit);
-    const rt_ray* d_rays = (const rt_ray*)mapped(rays, 16);
-    void* d_hits = mapped(hits, kind == kQueryAttr ? 16 : 8);
+    const size_t hit_bytes = (size_t)n * (kind == kQueryAttr ? sizeof(rt_hit_attr) : sizeof(rt_hit));
+    const rt_ray* d_rays = nullptr;
+    void* d_hits = nullptr;
     int rc = RT_OK;
-    if (!d_rays) {
-        if ((rc = ensure(c, c->d_qrays, c->qrays_cap, (size_t)n * 2))) return rc;
-        HIPC(c, hipMemcpyAsync(c->d_qrays, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-        d_rays = (const rt_ray*)c->d_qrays;
-    }
-    const bool back = !d_hits;
-    if (back) {   // d_qhits counts 8-B words: n of them for rt_hit, 8 n for rt_hit_attr
-        if ((rc = ensure(c, c->d_qhits, c->qhits_cap, (size_t)n * (rec / sizeof(uint2))))) return rc;
-        d_hits = c->d_qhits;
-    }
+    if ((rc = stage_in(c, rays, (size_t)n * sizeof(rt_ray), 16, c->d_qrays, c->qrays_cap, &d_rays))) return rc;
+    if ((rc = stage_dst(c, hits, hit_bytes, kind == kQueryAttr ? 16 : 8, &d_hits))) return rc;
     if ((rc = query_enqueue(c, kind, d_rays, n, flags, d_hits, c->stream))) return rc;
-    if (back) HIPC(c, hipMemcpyAsync(hits, d_hits, (size_t)n * rec, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = stage_out(c, hits, d_hits, hit_bytes))) return rc;
     HIPC(c, wait_ctx(c, c->stream));
     return RT_OK;
 }
@@ -3052,87 +3110,33 @@ int rt_trace_rays_attr(rt_ctx* c, const rt_ray* rays, int64_t n, uint32_t flags,
 }
 
 // ---- occlusion fans ----
-// A fan is a query to everything that waits for or reports on one: it takes the stream's kQueryKey slot
-// (spill columns, cursors, restart count, events, idle record) and becomes the context's last query.
 constexpr int64_t kMaxFanOrigins = 1ll << 26;
 constexpr uint32_t kFanFlags = RT_FLAG_HW_MATH | RT_FLAG_STRICT_MATH | RT_FLAG_EXACT_DIV;
 
-// the refusals that need no GPU; `who` names the entry point in the message
 static int fan_check(rt_ctx* c, const char* who, const void* origins, int64_t n, const void* dirs, int32_t k, uint32_t flags,
                      const void* masks) {
-    if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
-    if (n < 0 || n > kMaxFanOrigins) return set_err(c, std::string(who) + ": n must be 0..2^26", RT_ERR_INVALID_ARG);
+    if (const int rc = check_count(c, who, n, kMaxFanOrigins, "0..2^26")) return rc;
     if (n > 0 && (k < 1 || k > RT_FAN_MAX_DIRS))
         return set_err(c, std::string(who) + ": k must be 1..RT_FAN_MAX_DIRS", RT_ERR_INVALID_ARG);
     if (n > 0 && (!origins || !dirs || !masks)) return set_err(c, std::string(who) + ": origins, dirs or masks is NULL", RT_ERR_INVALID_ARG);
-    if (flags & ~kFanFlags) return set_err(c, std::string(who) + ": a flag that is not a fan's", RT_ERR_INVALID_ARG);
-    if ((flags & RT_FLAG_STRICT_MATH) && (flags & RT_FLAG_HW_MATH))
-        return set_err(c, std::string(who) + ": RT_FLAG_STRICT_MATH and RT_FLAG_HW_MATH exclude each other", RT_ERR_INVALID_ARG);
-    if (!c->have_scene) return set_err(c, std::string(who) + ": no scene uploaded", RT_ERR_NO_SCENE);
-    return RT_OK;
+    return check_flags_scene(c, who, flags, kFanFlags, ": a flag that is not a fan's");
 }
 
 // checked arguments, n > 0
 static int fan_enqueue(rt_ctx* c, const rt_fan_origin* d_origins, int64_t n, const rt_float4* d_dirs, int32_t k, uint32_t flags,
                        uint32_t* d_masks, hipStream_t s) {
-    int rc = RT_OK;
-    rt_ctx::FrameSlot* Lp = nullptr;
-    if ((rc = slot_for(c, (void*)s, kQueryKey, &Lp))) return rc;
-    rt_ctx::FrameSlot& L = *Lp;
     const int math = (flags & RT_FLAG_STRICT_MATH) ? 0 : (flags & RT_FLAG_HW_MATH) ? 1 : 2;
-    const Scene& sc = c->scene;
-    rtk::DevScene S{sc.wnodes(),
-                    sc.tris(),
-                    sc.shade(),
-                    sc.leaf(),
-                    (uint32_t)(sc.n_wnodes4 * 16),
-                    (uint32_t)(sc.rec_units() * 16),
-                    sc.root,
-                    sc.n_inner,
-                    (sc.fast_div && !(flags & RT_FLAG_EXACT_DIV)) ? 1 : 0,
-                    sc.clean};
-    const bool fast = S.clean != 0 && !sc.split;   // as for queries and frames
-    if (c->fan_grid_cap < 0) {   // RTAMD_FAN_GRID_BLOCKS=<b> (tests): at most b blocks, so that a wave takes many items
-        const char* v = std::getenv("RTAMD_FAN_GRID_BLOCKS");
-        const long b = v ? std::strtol(v, nullptr, 10) : 0;
-        c->fan_grid_cap = b > 0 && b < (1l << 20) ? (int)b : 0;
-    }
-    int& fgrid = c->fan_grid[math];
-    if (!fgrid) {
-        int cus = 0, b1 = 0;
-        HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, (const void*)kernel_fan(math, true), 256, 0));
-        fgrid = std::max(8, std::max(b1, 1) * cus * RTK_QUERY_GRID_PCT / 100);
-        if (c->fan_grid_cap) fgrid = std::min(fgrid, c->fan_grid_cap);
-    }
-    // the stack columns are sized for the mode's whole grid, whatever n and k are (ensure keeps a larger
-    // allocation, so fans and queries share the slot's columns)
-    const size_t full = (size_t)fgrid;
+    rtk::DevScene S = dev_scene(c->scene, flags);
+    void* kernel = kernel_fan(math, scene_fast(c->scene));
     const uint32_t chunks = ((uint32_t)k + 31u) / 32u;
     const uint32_t items = (uint32_t)((n + rtk::kSegRays - 1) / rtk::kSegRays) * chunks;   // <= 2^27
-    const uint32_t grid = (uint32_t)std::min<size_t>(full, (items + 3u) / 4u);
-    if ((rc = ensure(c, L.d_gstack, L.gstack_cap, full * rtk::kBlockThreads * rtk::kGlobalStack))) return rc;
-    if (!L.d_qcnt) {
-        size_t cap = 0;
-        if ((rc = ensure(c, L.d_qcnt, cap, rtk::kCursorSet + 32))) return rc;
-    }
-    for (hipEvent_t& e : L.qev)
-        if (!e) HIPC(c, hipEventCreate(&e));
-    rtk::Outputs O{};
-    O.gstack = L.d_gstack;
-    O.overflow = c->d_overflow;
-    O.restarts = L.d_qcnt + rtk::kCursorSet;
-    O.local_pixels = (uint64_t)grid * rtk::kBlockThreads;   // the stack's stride: the lanes launched
-    rtk::Fan Fn{(const float4*)d_origins, (const float4*)d_dirs, d_masks, (uint32_t)n, (uint32_t)k, chunks, L.d_qcnt};
-    HIPC(c, hipMemsetAsync(L.d_qcnt, 0, (rtk::kCursorSet + 32) * sizeof(uint32_t), s));
-    (void)hipGetLastError();
-    void* args[] = {&S, &O, &Fn};
-    HIPC(c, hipExtLaunchKernel(kernel_fan(math, fast), dim3(grid), dim3(rtk::kBlockThreads), args, 0, s, L.qev[0], L.qev[1], 0));
-    HIPC(c, hipGetLastError());
-    HIPC(c, hipEventRecord(L.idle, s));
-    c->query_slot = &L;
-    c->query_last = true;
-    return RT_OK;
+    return query_launch(c, s, c->fan_grid[math], kernel_fan(math, true), grid_cap("RTAMD_FAN_GRID_BLOCKS", c->fan_grid_cap), items,
+                        [&](rt_ctx::FrameSlot& L, uint32_t grid) {
+                            rtk::Outputs O = query_outputs(c, L, grid);
+                            rtk::Fan Fn{(const float4*)d_origins, (const float4*)d_dirs, d_masks, (uint32_t)n, (uint32_t)k, chunks, L.d_qcnt};
+                            void* args[] = {&S, &O, &Fn};
+                            return hipExtLaunchKernel(kernel, dim3(grid), dim3(rtk::kBlockThreads), args, 0, s, L.qev[0], L.qev[1], 0);
+                        });
 }
 
 int rt_trace_fan_device(rt_ctx* c, const rt_fan_origin* d_origins, int64_t n, const rt_float4* d_dirs, int32_t k, uint32_t flags,
@@ -3151,154 +3155,82 @@ int rt_trace_fan(rt_ctx* c, const rt_fan_origin* origins, int64_t n, const rt_fl
     if (const int rc = fan_check(c, "rt_trace_fan", origins, n, dirs, k, flags, masks)) return rc;
     if (n == 0) return RT_OK;
     HIPC(c, hipSetDevice(c->device));
-    // pinned, device-mapped caller memory is used directly, anything else is staged: as rt_trace_rays
-    auto mapped = [](const void* p, size_t align) -> void* {
-        hipPointerAttribute_t pa;
-        if (hipPointerGetAttributes(&pa, p) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer &&
-            !((uintptr_t)pa.devicePointer & (align - 1)))
-            return pa.devicePointer;
-        (void)hipGetLastError();   // pageable memory: not an error
-        return nullptr;
-    };
-    const size_t words = (size_t)(((uint32_t)k + 31u) / 32u) * (size_t)n;
-    const rt_fan_origin* d_origins = (const rt_fan_origin*)mapped(origins, 16);
-    const rt_float4* d_dirs = (const rt_float4*)mapped(dirs, 16);
-    uint32_t* d_masks = (uint32_t*)mapped(masks, 4);
+    const size_t mask_bytes = (size_t)(((uint32_t)k + 31u) / 32u) * (size_t)n * sizeof(uint32_t);
+    const rt_fan_origin* d_origins = nullptr;
+    const rt_float4* d_dirs = nullptr;
+    uint32_t* d_masks = nullptr;
     int rc = RT_OK;
-    if (!d_origins) {
-        if ((rc = ensure(c, c->d_qrays, c->qrays_cap, (size_t)n * 2))) return rc;
-        HIPC(c, hipMemcpyAsync(c->d_qrays, origins, (size_t)n * sizeof(rt_fan_origin), hipMemcpyHostToDevice, c->stream));
-        d_origins = (const rt_fan_origin*)c->d_qrays;
-    }
-    if (!d_dirs) {
-        if ((rc = ensure(c, c->d_fdirs, c->fdirs_cap, (size_t)k))) return rc;
-        HIPC(c, hipMemcpyAsync(c->d_fdirs, dirs, (size_t)k * sizeof(rt_float4), hipMemcpyHostToDevice, c->stream));
-        d_dirs = (const rt_float4*)c->d_fdirs;
-    }
-    const bool back = !d_masks;
-    if (back) {   // d_qhits counts 8-B words
-        if ((rc = ensure(c, c->d_qhits, c->qhits_cap, (words + 1) / 2))) return rc;
-        d_masks = (uint32_t*)c->d_qhits;
-    }
+    if ((rc = stage_in(c, origins, (size_t)n * sizeof(rt_fan_origin), 16, c->d_qrays, c->qrays_cap, &d_origins))) return rc;
+    if ((rc = stage_in(c, dirs, (size_t)k * sizeof(rt_float4), 16, c->d_fdirs, c->fdirs_cap, &d_dirs))) return rc;
+    if ((rc = stage_dst(c, masks, mask_bytes, 4, &d_masks))) return rc;
     if ((rc = fan_enqueue(c, d_origins, n, d_dirs, k, flags, d_masks, c->stream))) return rc;
-    if (back) HIPC(c, hipMemcpyAsync(masks, d_masks, words * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = stage_out(c, masks, d_masks, mask_bytes))) return rc;
     HIPC(c, wait_ctx(c, c->stream));
     return RT_OK;
 }
 
 // ---- closest-point queries ----
-// A point query is a query to everything that waits for or reports on one, as a fan is: it takes the
-// stream's kQueryKey slot (spill columns, cursors, restart count, events, idle record) and becomes the
-// context's last query.  Its kernel (rt_closest.hip) restarts nothing: the slot's restart count stays 0.
+// The point kernels (rt_closest.hip) restart nothing: the slot's restart count stays 0.
 static_assert(rtclosest::kThreads == rtk::kBlockThreads && rtclosest::kGlobalStack == rtk::kGlobalStack &&
                   rtclosest::kCursors == rtk::kCursors && rtclosest::kCursorStride == rtk::kCursorStride,
               "rt_closest.hip shares the query slot's spill columns and cursors");
 
-// the refusals that need no GPU; `who` names the entry point in the message
 static int closest_check(rt_ctx* c, const char* who, const void* pts, int64_t n, uint32_t flags, const void* out) {
-    if (!c) return set_err(nullptr, std::string(who) + ": ctx is NULL", RT_ERR_INVALID_ARG);
-    if (n < 0 || n > kMaxQueryRays) return set_err(c, std::string(who) + ": n must be 0..2^30", RT_ERR_INVALID_ARG);
+    if (const int rc = check_count(c, who, n, kMaxQueryRays, "0..2^30")) return rc;
     if (n > 0 && (!pts || !out)) return set_err(c, std::string(who) + ": pts or out is NULL", RT_ERR_INVALID_ARG);
-    if (flags) return set_err(c, std::string(who) + ": flags must be 0", RT_ERR_INVALID_ARG);
-    if (!c->have_scene) return set_err(c, std::string(who) + ": no scene uploaded", RT_ERR_NO_SCENE);
-    return RT_OK;
+    return check_flags_scene(c, who, flags, 0, ": flags must be 0");
 }
 
 // checked arguments, n > 0.  k == 0: rt_closest_points' kernel and one record per point; k in 1 ..
 // RT_NEAREST_MAX_K: rt_nearest_k's kernel of that k and k planes of n records.
 static int points_enqueue(rt_ctx* c, const rt_point* d_pts, int64_t n, int k, rt_closest* d_out, hipStream_t s) {
-    int rc = RT_OK;
-    rt_ctx::FrameSlot* Lp = nullptr;
-    if ((rc = slot_for(c, (void*)s, kQueryKey, &Lp))) return rc;
-    rt_ctx::FrameSlot& L = *Lp;
     const Scene& sc = c->scene;
-    if (c->closest_grid_cap < 0) {   // RTAMD_CLOSEST_GRID_BLOCKS=<b> (tests): at most b blocks, so that a wave takes many groups
-        const char* v = std::getenv("RTAMD_CLOSEST_GRID_BLOCKS");
-        const long b = v ? std::strtol(v, nullptr, 10) : 0;
-        c->closest_grid_cap = b > 0 && b < (1l << 20) ? (int)b : 0;
-    }
-    int& cgrid = k ? c->nearest_grid[k - 1] : c->closest_grid;
-    if (!cgrid) {
-        int cus = 0, b1 = 0;
-        HIPC(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        HIPC(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&b1, k ? rtclosest::nearest_kernel_of(k) : rtclosest::kernel(),
-                                                             rtclosest::kThreads, 0));
-        cgrid = std::max(8, std::max(b1, 1) * cus * RTK_QUERY_GRID_PCT / 100);
-        if (c->closest_grid_cap) cgrid = std::min(cgrid, c->closest_grid_cap);
-    }
-    // the stack columns are sized for the whole grid, whatever n is (ensure keeps a larger allocation, so
-    // point queries, fans and ray queries share the slot's columns)
-    const size_t full = (size_t)cgrid;
-    const uint32_t ngroups = (uint32_t)((n + rtk::kSegRays - 1) / rtk::kSegRays);
-    const uint32_t grid = (uint32_t)std::min<size_t>(full, (ngroups + 3u) / 4u);
-    if ((rc = ensure(c, L.d_gstack, L.gstack_cap, full * rtk::kBlockThreads * rtk::kGlobalStack))) return rc;
-    if (!L.d_qcnt) {
-        size_t cap = 0;
-        if ((rc = ensure(c, L.d_qcnt, cap, rtk::kCursorSet + 32))) return rc;
-    }
-    for (hipEvent_t& e : L.qev)
-        if (!e) HIPC(c, hipEventCreate(&e));
     const rtclosest::Scene S{sc.wnodes(), sc.tris(), sc.leaf(), sc.root};
-    const rtclosest::Launch Q{(const float4*)d_pts, (float4*)d_out, (uint32_t)n, L.d_qcnt, L.d_gstack, c->d_overflow};
-    HIPC(c, hipMemsetAsync(L.d_qcnt, 0, (rtk::kCursorSet + 32) * sizeof(uint32_t), s));
-    (void)hipGetLastError();
-    if (k) HIPC(c, rtclosest::launch_nearest(S, Q, k, grid, s, L.qev[0], L.qev[1]));
-    else HIPC(c, rtclosest::launch(S, Q, grid, s, L.qev[0], L.qev[1]));
-    HIPC(c, hipEventRecord(L.idle, s));
-    c->query_slot = &L;
-    c->query_last = true;
-    return RT_OK;
+    const uint32_t ngroups = (uint32_t)((n + rtk::kSegRays - 1) / rtk::kSegRays);
+    return query_launch(c, s, k ? c->nearest_grid[k - 1] : c->closest_grid, rtclosest::kernel(k),
+                        grid_cap("RTAMD_CLOSEST_GRID_BLOCKS", c->closest_grid_cap), ngroups,
+                        [&](rt_ctx::FrameSlot& L, uint32_t grid) {
+                            const rtclosest::Launch Q{(const float4*)d_pts, (float4*)d_out, (uint32_t)n, L.d_qcnt, L.d_gstack, c->d_overflow};
+                            return rtclosest::launch(S, Q, k, grid, s, L.qev[0], L.qev[1]);
+                        });
 }
 
-static int closest_enqueue(rt_ctx* c, const rt_point* d_pts, int64_t n, rt_closest* d_out, hipStream_t s) {
-    return points_enqueue(c, d_pts, n, 0, d_out, s);
-}
-
-// pinned, device-mapped caller memory is used directly, anything else is staged: as rt_trace_rays
-static void* mapped_host(const void* p, size_t align) {
-    hipPointerAttribute_t pa;
-    if (hipPointerGetAttributes(&pa, p) == hipSuccess && pa.type == hipMemoryTypeHost && pa.devicePointer &&
-        !((uintptr_t)pa.devicePointer & (align - 1)))
-        return pa.devicePointer;
-    (void)hipGetLastError();   // pageable memory: not an error
-    return nullptr;
-}
-
-int rt_closest_points_device(rt_ctx* c, const rt_point* d_pts, int64_t n, uint32_t flags, rt_closest* d_out, void* stream) {
-    if (const int rc = closest_check(c, "rt_closest_points_device", d_pts, n, flags, d_out)) return rc;
+// the two entry points of rt_closest_points (k == 0) and rt_nearest_k, after their checks
+static int points_device(rt_ctx* c, const char* who, const rt_point* d_pts, int64_t n, int k, rt_closest* d_out, void* stream) {
     if (n == 0) return RT_OK;
     if (((uintptr_t)d_pts & 15u) || ((uintptr_t)d_out & 15u))
-        return set_err(c, "rt_closest_points_device: d_pts and d_out must be 16-byte aligned", RT_ERR_INVALID_ARG);
+        return set_err(c, std::string(who) + ": d_pts and d_out must be 16-byte aligned", RT_ERR_INVALID_ARG);
     HIPC(c, hipSetDevice(c->device));
-    return closest_enqueue(c, d_pts, n, d_out, stream ? (hipStream_t)stream : c->stream);
+    return points_enqueue(c, d_pts, n, k, d_out, stream ? (hipStream_t)stream : c->stream);
 }
 
-int rt_closest_points(rt_ctx* c, const rt_point* pts, int64_t n, uint32_t flags, rt_closest* out) {
-    if (const int rc = closest_check(c, "rt_closest_points", pts, n, flags, out)) return rc;
+static int points_host(rt_ctx* c, const rt_point* pts, int64_t n, int k, rt_closest* out) {
     if (n == 0) return RT_OK;
     HIPC(c, hipSetDevice(c->device));
-    const rt_point* d_pts = (const rt_point*)mapped_host(pts, 16);
-    rt_closest* d_out = (rt_closest*)mapped_host(out, 16);
+    const size_t out_bytes = (size_t)n * (size_t)(k ? k : 1) * sizeof(rt_closest);
+    const rt_point* d_pts = nullptr;
+    rt_closest* d_out = nullptr;
     int rc = RT_OK;
-    if (!d_pts) {   // d_qrays counts 16-B words
-        if ((rc = ensure(c, c->d_qrays, c->qrays_cap, (size_t)n))) return rc;
-        HIPC(c, hipMemcpyAsync(c->d_qrays, pts, (size_t)n * sizeof(rt_point), hipMemcpyHostToDevice, c->stream));
-        d_pts = (const rt_point*)c->d_qrays;
-    }
-    const bool back = !d_out;
-    if (back) {   // d_qhits counts 8-B words
-        if ((rc = ensure(c, c->d_qhits, c->qhits_cap, (size_t)n * (sizeof(rt_closest) / sizeof(uint2))))) return rc;
-        d_out = (rt_closest*)c->d_qhits;
-    }
-    if ((rc = closest_enqueue(c, d_pts, n, d_out, c->stream))) return rc;
-    if (back) HIPC(c, hipMemcpyAsync(out, d_out, (size_t)n * sizeof(rt_closest), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = stage_in(c, pts, (size_t)n * sizeof(rt_point), 16, c->d_qrays, c->qrays_cap, &d_pts))) return rc;
+    if ((rc = stage_dst(c, out, out_bytes, 16, &d_out))) return rc;
+    if ((rc = points_enqueue(c, d_pts, n, k, d_out, c->stream))) return rc;
+    if ((rc = stage_out(c, out, d_out, out_bytes))) return rc;
     HIPC(c, wait_ctx(c, c->stream));
     return RT_OK;
 }
 
+int rt_closest_points_device(rt_ctx* c, const rt_point* d_pts, int64_t n, uint32_t flags, rt_closest* d_out, void* stream) {
+    if (const int rc = closest_check(c, "rt_closest_points_device", d_pts, n, flags, d_out)) return rc;
+    return points_device(c, "rt_closest_points_device", d_pts, n, 0, d_out, stream);
+}
+
+int rt_closest_points(rt_ctx* c, const rt_point* pts, int64_t n, uint32_t flags, rt_closest* out) {
+    if (const int rc = closest_check(c, "rt_closest_points", pts, n, flags, out)) return rc;
+    return points_host(c, pts, n, 0, out);
+}
+
 // ---- k nearest triangles ----
-// rt_closest_points with k records per point, in k planes of n: the same slot, grid rule, staging and
-// events; the kernel is rt_closest.hip's nearest_kernel<k>.
+// rt_closest_points with k records per point, in k planes of n; the kernel is rt_closest.hip's nearest_kernel<k>.
 static int nearest_check(rt_ctx* c, const char* who, const void* pts, int64_t n, int32_t k, uint32_t flags, const void* out) {
     if (const int rc = closest_check(c, who, pts, n, flags, out)) return rc;
     if (k < 1 || k > RT_NEAREST_MAX_K) return set_err(c, std::string(who) + ": k must be 1..8", RT_ERR_INVALID_ARG);
@@ -3306,41 +3238,14 @@ static int nearest_check(rt_ctx* c, const char* who, const void* pts, int64_t n,
     return RT_OK;
 }
 
-static int nearest_enqueue(rt_ctx* c, const rt_point* d_pts, int64_t n, int32_t k, rt_closest* d_out, hipStream_t s) {
-    return points_enqueue(c, d_pts, n, k, d_out, s);
-}
-
 int rt_nearest_k_device(rt_ctx* c, const rt_point* d_pts, int64_t n, int32_t k, uint32_t flags, rt_closest* d_out, void* stream) {
     if (const int rc = nearest_check(c, "rt_nearest_k_device", d_pts, n, k, flags, d_out)) return rc;
-    if (n == 0) return RT_OK;
-    if (((uintptr_t)d_pts & 15u) || ((uintptr_t)d_out & 15u))
-        return set_err(c, "rt_nearest_k_device: d_pts and d_out must be 16-byte aligned", RT_ERR_INVALID_ARG);
-    HIPC(c, hipSetDevice(c->device));
-    return nearest_enqueue(c, d_pts, n, k, d_out, stream ? (hipStream_t)stream : c->stream);
+    return points_device(c, "rt_nearest_k_device", d_pts, n, k, d_out, stream);
 }
 
 int rt_nearest_k(rt_ctx* c, const rt_point* pts, int64_t n, int32_t k, uint32_t flags, rt_closest* out) {
     if (const int rc = nearest_check(c, "rt_nearest_k", pts, n, k, flags, out)) return rc;
-    if (n == 0) return RT_OK;
-    HIPC(c, hipSetDevice(c->device));
-    const rt_point* d_pts = (const rt_point*)mapped_host(pts, 16);
-    rt_closest* d_out = (rt_closest*)mapped_host(out, 16);
-    int rc = RT_OK;
-    if (!d_pts) {   // d_qrays counts 16-B words
-        if ((rc = ensure(c, c->d_qrays, c->qrays_cap, (size_t)n))) return rc;
-        HIPC(c, hipMemcpyAsync(c->d_qrays, pts, (size_t)n * sizeof(rt_point), hipMemcpyHostToDevice, c->stream));
-        d_pts = (const rt_point*)c->d_qrays;
-    }
-    const size_t nrec = (size_t)n * (size_t)k;
-    const bool back = !d_out;
-    if (back) {   // d_qhits counts 8-B words
-        if ((rc = ensure(c, c->d_qhits, c->qhits_cap, nrec * (sizeof(rt_closest) / sizeof(uint2))))) return rc;
-        d_out = (rt_closest*)c->d_qhits;
-    }
-    if ((rc = nearest_enqueue(c, d_pts, n, k, d_out, c->stream))) return rc;
-    if (back) HIPC(c, hipMemcpyAsync(out, d_out, nrec * sizeof(rt_closest), hipMemcpyDeviceToHost, c->stream));
-    HIPC(c, wait_ctx(c, c->stream));
-    return RT_OK;
+    return points_host(c, pts, n, k, out);
 }
 
 int rt_last_query_timing(rt_ctx* c, float* ms) {
