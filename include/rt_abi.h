@@ -729,6 +729,37 @@ int rt_nearest_k_host(const rt_float4* verts, int32_t nv, const int32_t* idx, in
                       const rt_bvh_node* nodes, int32_t nn, const int32_t* refs, int32_t nref,
                       const rt_point* pts, int64_t n, int32_t k, rt_closest* out, uint64_t* stats3);
 
+/* ---- first k hits ----
+ * rt_trace_rays' closest hit with k answers per ray: the first k DISTINCT triangles along the ray with
+ * 0.001f < t < tmax, ordered by (t, id), each with ray_tri's barycentrics u, v (the hit is
+ * (1 - u - v) p0 + u p1 + v p2): what lies behind the first surface, without re-launching the ray.
+ * out holds k planes of n records: out[j * n + i] is the j-th hit of ray i, j = 0 the nearest; entries
+ * beyond the number found are the miss record {-1, the ray's tmax word, 0, 0}.  Rays, the validity rule
+ * and `reserved` are rt_trace_rays'; an invalid ray gives k miss records.  A triangle that the tree
+ * references from several leaves appears once, and of two triangles at the same t the lower id comes
+ * first.  With k = 1 the t word is rt_trace_rays' closest-hit t for every ray in every arithmetic (the
+ * id is the lower one where two triangles tie); but k = 1 runs the general traversal loop, so a caller
+ * who needs one hit should call rt_trace_rays, which is faster.  A stack overflow or a malformed inner
+ * node makes all k records of the ray a miss; the overflow is counted once.
+ *
+ * flags: RT_FLAG_HW_MATH or RT_FLAG_STRICT_MATH (not both) and RT_FLAG_EXACT_DIV; any other bit,
+ * RT_FLAG_ANY_HIT included, is RT_ERR_INVALID_ARG.  Refused before any GPU work with
+ * RT_ERR_INVALID_ARG: everything rt_trace_rays refuses, k outside 1..RT_TRACE_MAX_K (also with
+ * n == 0), n * k > 2^30, a device pointer that is not 16-byte aligned; RT_ERR_NO_SCENE without a
+ * scene.  n == 0 returns RT_OK and launches nothing.  Synchrony, the pinned shortcut, streams, the
+ * slot, rt_last_query_timing and rt_overflow_count behave as for rt_trace_rays[_device];
+ * rt_last_deferred reports 0: nothing restarts.
+ * rt_trace_rays_k_host is the definition in host code over the caller's scene arrays, in S_strict: no
+ * context, no GPU; stats3 (may be NULL) receives {overflows, inner visits, triangle tests}. */
+typedef struct rt_hit_uv { int32_t id; float t, u, v; } rt_hit_uv;   /* 16 B */
+#define RT_TRACE_MAX_K 8
+int rt_trace_rays_k(rt_ctx* ctx, const rt_ray* rays, int64_t n, int32_t k, uint32_t flags, rt_hit_uv* out);
+int rt_trace_rays_k_device(rt_ctx* ctx, const rt_ray* d_rays, int64_t n, int32_t k, uint32_t flags,
+                           rt_hit_uv* d_out, void* stream);
+int rt_trace_rays_k_host(const rt_float4* verts, int32_t nv, const int32_t* idx, int32_t nidx,
+                         const rt_bvh_node* nodes, int32_t nn, const int32_t* refs, int32_t nref,
+                         const rt_ray* rays, int64_t n, int32_t k, rt_hit_uv* out, uint64_t* stats3);
+
 /* Traversals of the last frame (or of the last ray query, if that came later) that outgrew the
  * fast kernel's LDS stack and restarted in-kernel with the general traversal (same result,
  * slower ray); diagnostics, synchronizes the stream. */

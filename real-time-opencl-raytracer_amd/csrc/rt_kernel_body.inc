@@ -1327,4 +1327,92 @@ __global__ void __launch_bounds__(256, kMath == 2 ? RTK_FAN_REF_WAVES : RTK_FAN_
     }
 }
 
+// ============================================================================
+// First k hits (rt_trace_rays_k, DESIGN.md 24): for each ray the first K distinct triangles along it,
+// ordered by (t, id), with u and v.  The list and the control flow are csrc/host/multihit_core.hpp's, the
+// text the host twin runs; this namespace's arithmetic comes in through RayScene, which is the general
+// traverse<true>'s: ray_init, its choice between the fast quotient and the division form, its slab
+// test, ray_tri.  query_kernel's persistent grid, cursor grab, ray loads and validity test; the stack
+// is the general traversal's Stack (16 LDS rows per lane, then the slot's global columns: no guard rows,
+// which only traverse_ifif touches).  Lanes step independently, one step per trip (if-if, as
+// closest_kernel: the bound is the lane's own).  At the end a lane evaluates ray_tri_uv for the
+// entries it found and stores plane j of its ray to out[j * n + i], one 16-B store per plane, a wave's
+// 1 KiB contiguous.  One instantiation per K, so the list is indexed statically only.  Nothing restarts:
+// O.restarts stays 0.
+// A caller who needs one hit should call rt_trace_rays: K = 1 runs this general loop, not the fast one.
+// ============================================================================
+struct RayScene {
+    const DevScene& S;
+    const Ray& ray;
+    const F3 y;        // slab_recip(ray)
+    const bool fast;   // traverse's choice: S.fast_div && fast_div_ok(ray)
+    __device__ __forceinline__ void slab(uint32_t cur, float& n0, float& f0, float& n1, float& f1, uint32_t& r0, uint32_t& r1) const {
+        const float4* np = S.wnodes + (size_t)cur * 4;
+        const float4 q0 = np[0], q1 = np[1], q2 = np[2], q3 = np[3];
+        if (fast) slab2_pk<true>(q0, q1, q2, ray_pk(ray.ori, ray.dir, y), n0, f0, n1, f1);
+        else slab2_div(q0, q1, q2, ray.ori, ray.dir, n0, f0, n1, f1);
+        r0 = __float_as_uint(q3.x);
+        r1 = __float_as_uint(q3.y);
+    }
+    __device__ __forceinline__ void leaf(uint32_t ref, int& off, int& cnt) const { leaf_range(S, ref, off, cnt); }
+    __device__ __forceinline__ void tri_t(int k, float& t, int32_t& id) const {
+        const float4* tp = tri_rec(S, k);
+        const float4 a0 = tp[0], a1 = tp[1], a2 = tp[2];
+        t = ray_tri(ray, F3{a0.x, a0.y, a0.z}, F3{a1.x, a1.y, a1.z}, F3{a2.x, a2.y, a2.z});
+        id = __float_as_int(a0.w);
+    }
+};
+
+// waves per SIMD multihit_kernel<K> is bounded to: what its registers allow without scratch (DESIGN.md 24)
+constexpr int multihit_waves(int k) {
+    return kMath == 2 ? RTK_MULTIHIT_REF_WAVES(k) : RTK_MULTIHIT_WAVES(k);
+}
+
+template <int K>
+__global__ void __launch_bounds__(256, multihit_waves(K)) multihit_kernel(DevScene S, Outputs O, rtk::Query Q) {
+    __shared__ uint32_t s_stack[4][kLdsStack][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t ngroups = (Q.n + rtk::kSegRays - 1) / rtk::kSegRays;
+    uint32_t home = blockIdx.x & (rtk::kCursors - 1u);
+    Stack st;
+    st.lds = &s_stack[wave][0][lane];
+    st.glb = O.gstack + ((size_t)blockIdx.x * rtk::kBlockThreads + threadIdx.x);
+    st.gstride = O.local_pixels;   // the lanes launched
+    uint4* const out = (uint4*)Q.hits;
+    for (;;) {
+        const uint32_t g = rtk::grab_group(Q.fetch, ngroups, home);
+        if (g == rtk::kNoGroup) break;
+        const uint32_t i = g * rtk::kSegRays + (uint32_t)lane;
+        const bool inside = i < Q.n;   // (false only in the last group's tail)
+        float4 a = make_float4(0, 0, 0, 0), b = a;
+        if (inside) {
+            const float4* rp = Q.rays + (size_t)i * 2;
+            a = rp[0];
+            b = rp[1];
+        }
+        const bool traced = inside && query_ray_ok(a, b);
+        const Ray ray = ray_init(F3{a.x, a.y, a.z}, F3{b.x, b.y, b.z});   // (an untraced lane's is never used)
+        const RayScene RS{S, ray, slab_recip(ray), S.fast_div && fast_div_ok(ray)};
+        multihit::StateK<K> T;
+        multihit::start(T, S.root, a.w);
+        if (!traced) T.sc = 0;
+        while (T.sc > 0) multihit::step<false>(T, RS, st);
+        if (inside) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                uint4 w = make_uint4(0xFFFFFFFFu, __float_as_uint(a.w), 0u, 0u);   // the miss record: the ray's tmax word
+                if (T.id[j] >= 0) {
+                    const float4* tp = tri_rec(S, T.at[j]);
+                    const float4 a0 = tp[0], a1 = tp[1], a2 = tp[2];
+                    float u, v;
+                    ray_tri_uv(ray, F3{a0.x, a0.y, a0.z}, F3{a1.x, a1.y, a1.z}, F3{a2.x, a2.y, a2.z}, u, v);
+                    w = make_uint4((uint32_t)T.id[j], __float_as_uint(T.t[j]), __float_as_uint(u), __float_as_uint(v));
+                }
+                out[(size_t)j * Q.n + i] = w;
+            }
+        }
+        if (T.overflow) atomicAdd(O.overflow, 1ull);
+    }
+}
+
 }  // namespace RTK_NS

@@ -58,6 +58,8 @@
 #include "rt_sah.h"
 #include "rt_closest.h"
 #include "lbvh_core.hpp"
+#define MULTIHIT_HD __device__ __forceinline__
+#include "multihit_core.hpp"
 
 #ifndef RTK_WF_WAVES
 #define RTK_WF_WAVES 7      // waves per SIMD the wavefront kernels are bounded to
@@ -91,6 +93,13 @@
 #endif
 #ifndef RTK_FAN_WAVES
 #define RTK_FAN_WAVES 6         // the same for S_strict / S_hw: at 7 their fast kernels spill 12 / 24 B
+#endif
+#ifndef RTK_MULTIHIT_REF_WAVES
+// waves per SIMD S_ref's multihit_kernel<k> is bounded to: the most at which it has no scratch
+#define RTK_MULTIHIT_REF_WAVES(k) ((k) <= 2 ? 8 : (k) == 3 ? 7 : (k) == 4 ? 6 : (k) <= 7 ? 5 : 4)
+#endif
+#ifndef RTK_MULTIHIT_WAVES
+#define RTK_MULTIHIT_WAVES(k) ((k) == 1 ? 8 : (k) == 2 ? 7 : (k) == 3 ? 6 : (k) <= 5 ? 5 : 4)   // the same for S_strict / S_hw
 #endif
 #ifndef RTK_QUERY_GRID_PCT
 #define RTK_QUERY_GRID_PCT 75   // persistent query grid, percent of the blocks the chip holds at once (C3's 2.07 M primary
@@ -1171,6 +1180,8 @@ struct rt_ctx {
     int closest_grid = 0;                            // rt_closest_points
     int nearest_grid[RT_NEAREST_MAX_K] = {};         // rt_nearest_k: [k - 1]
     int closest_grid_cap = -1;                       //   RTAMD_CLOSEST_GRID_BLOCKS, both point families
+    int multihit_grid[3][RT_TRACE_MAX_K] = {};       // rt_trace_rays_k: [math][k - 1]
+    int multihit_grid_cap = -1;                      //   RTAMD_MULTIHIT_GRID_BLOCKS
     // The host forms' staging (stage_in, stage_dst, stage_out), shared by every family, grow-only,
     // capacities in bytes: d_qrays takes the rays, fan origins or points, d_fdirs a fan's direction
     // table, d_qhits gives the hits, masks or records back
@@ -1502,6 +1513,13 @@ template <int M> struct Kernels;
                        : (fast ? (void*)NS::query_attr_kernel<false, true> : (void*)NS::query_attr_kernel<false, false>); \
         }                                                                                                  \
         static void* fan(bool fast) { return fast ? (void*)NS::fan_kernel<true> : (void*)NS::fan_kernel<false>; } \
+        static void* multihit(int k) {                                                                     \
+            void* const t[RT_TRACE_MAX_K] = {(void*)NS::multihit_kernel<1>, (void*)NS::multihit_kernel<2>, \
+                                             (void*)NS::multihit_kernel<3>, (void*)NS::multihit_kernel<4>, \
+                                             (void*)NS::multihit_kernel<5>, (void*)NS::multihit_kernel<6>, \
+                                             (void*)NS::multihit_kernel<7>, (void*)NS::multihit_kernel<8>}; \
+            return t[k - 1];                                                                               \
+        }                                                                                                  \
         static void* batch(bool fast, bool next) {                                                         \
             return fast ? (next ? (void*)NS::first_bounce_batch_kernel<true, true> : (void*)NS::first_bounce_batch_kernel<true, false>) \
                         : (next ? (void*)NS::first_bounce_batch_kernel<false, true> : (void*)NS::first_bounce_batch_kernel<false, false>); \
@@ -1538,6 +1556,9 @@ static void* kernel_query_attr(int m, bool any, bool fast) {
 }
 static void* kernel_fan(int m, bool fast) {
     return m == 0 ? Kernels<0>::fan(fast) : m == 1 ? Kernels<1>::fan(fast) : Kernels<2>::fan(fast);
+}
+static void* kernel_multihit(int m, int k) {
+    return m == 0 ? Kernels<0>::multihit(k) : m == 1 ? Kernels<1>::multihit(k) : Kernels<2>::multihit(k);
 }
 // the timeline instantiation (rt_wave_timeline): S_ref, the fast kernels
 static void* kernel_timeline_first(bool next, bool walk) {
@@ -2937,7 +2958,7 @@ static int check_flags_scene(rt_ctx* c, const char* who, uint32_t flags, uint32_
     return RT_OK;
 }
 
-// RTAMD_FAN_GRID_BLOCKS, RTAMD_CLOSEST_GRID_BLOCKS = <b> (tests): at most b blocks in the family's grids,
+// RTAMD_FAN_GRID_BLOCKS, RTAMD_CLOSEST_GRID_BLOCKS, RTAMD_MULTIHIT_GRID_BLOCKS = <b> (tests): at most b blocks in the family's grids,
 // so that a wave takes many items.  Read once per context (memo -1: not read yet); 0: no cap.
 static int grid_cap(const char* var, int& memo) {
     if (memo < 0) {
@@ -3107,6 +3128,60 @@ int rt_trace_rays_attr_device(rt_ctx* c, const rt_ray* d_rays, int64_t n, uint32
 
 int rt_trace_rays_attr(rt_ctx* c, const rt_ray* rays, int64_t n, uint32_t flags, rt_hit_attr* hits) {
     return trace_rays_host(c, kQueryAttr, "rt_trace_rays_attr", rays, n, flags, hits);
+}
+
+// ---- first k hits ----
+// rt_trace_rays with k records per ray, in k planes of n: the same slot, staging and events; the kernel is
+// multihit_kernel<k> of the arithmetic the flags name, and its grid is that kernel's own.
+constexpr uint32_t kMultihitFlags = RT_FLAG_HW_MATH | RT_FLAG_STRICT_MATH | RT_FLAG_EXACT_DIV;
+
+static int multihit_check(rt_ctx* c, const char* who, const void* rays, int64_t n, int32_t k, uint32_t flags, const void* out) {
+    if (const int rc = check_count(c, who, n, kMaxQueryRays, "0..2^30")) return rc;
+    if (n > 0 && (!rays || !out)) return set_err(c, std::string(who) + ": rays or out is NULL", RT_ERR_INVALID_ARG);
+    if (const int rc = check_flags_scene(c, who, flags, kMultihitFlags, ": a flag that is not a first-k-hits query's")) return rc;
+    if (k < 1 || k > RT_TRACE_MAX_K) return set_err(c, std::string(who) + ": k must be 1..8", RT_ERR_INVALID_ARG);
+    if (n * k > kMaxQueryRays) return set_err(c, std::string(who) + ": n * k must be at most 2^30", RT_ERR_INVALID_ARG);
+    return RT_OK;
+}
+
+// checked arguments, n > 0
+static int multihit_enqueue(rt_ctx* c, const rt_ray* d_rays, int64_t n, int32_t k, uint32_t flags, rt_hit_uv* d_out, hipStream_t s) {
+    const int math = (flags & RT_FLAG_STRICT_MATH) ? 0 : (flags & RT_FLAG_HW_MATH) ? 1 : 2;
+    rtk::DevScene S = dev_scene(c->scene, flags);
+    void* kernel = kernel_multihit(math, k);
+    const uint32_t ngroups = (uint32_t)((n + rtk::kSegRays - 1) / rtk::kSegRays);
+    return query_launch(c, s, c->multihit_grid[math][k - 1], kernel, grid_cap("RTAMD_MULTIHIT_GRID_BLOCKS", c->multihit_grid_cap),
+                        ngroups, [&](rt_ctx::FrameSlot& L, uint32_t grid) {
+                            rtk::Outputs O = query_outputs(c, L, grid);
+                            rtk::Query Q{(const float4*)d_rays, (uint2*)d_out, (uint32_t)n, L.d_qcnt};
+                            void* args[] = {&S, &O, &Q};
+                            return hipExtLaunchKernel(kernel, dim3(grid), dim3(rtk::kBlockThreads), args, 0, s, L.qev[0], L.qev[1], 0);
+                        });
+}
+
+int rt_trace_rays_k_device(rt_ctx* c, const rt_ray* d_rays, int64_t n, int32_t k, uint32_t flags, rt_hit_uv* d_out, void* stream) {
+    if (const int rc = multihit_check(c, "rt_trace_rays_k_device", d_rays, n, k, flags, d_out)) return rc;
+    if (n == 0) return RT_OK;
+    if (((uintptr_t)d_rays & 15u) || ((uintptr_t)d_out & 15u))
+        return set_err(c, "rt_trace_rays_k_device: d_rays and d_out must be 16-byte aligned", RT_ERR_INVALID_ARG);
+    HIPC(c, hipSetDevice(c->device));
+    return multihit_enqueue(c, d_rays, n, k, flags, d_out, stream ? (hipStream_t)stream : c->stream);
+}
+
+int rt_trace_rays_k(rt_ctx* c, const rt_ray* rays, int64_t n, int32_t k, uint32_t flags, rt_hit_uv* out) {
+    if (const int rc = multihit_check(c, "rt_trace_rays_k", rays, n, k, flags, out)) return rc;
+    if (n == 0) return RT_OK;
+    HIPC(c, hipSetDevice(c->device));
+    const size_t out_bytes = (size_t)n * (size_t)k * sizeof(rt_hit_uv);
+    const rt_ray* d_rays = nullptr;
+    rt_hit_uv* d_out = nullptr;
+    int rc = RT_OK;
+    if ((rc = stage_in(c, rays, (size_t)n * sizeof(rt_ray), 16, c->d_qrays, c->qrays_cap, &d_rays))) return rc;
+    if ((rc = stage_dst(c, out, out_bytes, 16, &d_out))) return rc;
+    if ((rc = multihit_enqueue(c, d_rays, n, k, flags, d_out, c->stream))) return rc;
+    if ((rc = stage_out(c, out, d_out, out_bytes))) return rc;
+    HIPC(c, wait_ctx(c, c->stream));
+    return RT_OK;
 }
 
 // ---- occlusion fans ----

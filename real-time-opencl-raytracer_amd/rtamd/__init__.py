@@ -82,6 +82,10 @@ class rt_hit(C.Structure):
     _fields_ = [("id", C.c_int32), ("t", C.c_float)]
 
 
+class rt_hit_uv(C.Structure):
+    _fields_ = [("id", C.c_int32), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float)]
+
+
 class rt_point(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("r", C.c_float)]
 
@@ -101,6 +105,7 @@ class rt_hit_attr(C.Structure):
 # the same records as numpy dtypes (trace_rays' and trace_rays_attr's buffers)
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("reserved", np.uint32)])
 HIT_DTYPE = np.dtype([("id", np.int32), ("t", np.float32)])
+HIT_UV_DTYPE = np.dtype([("id", np.int32), ("t", np.float32), ("u", np.float32), ("v", np.float32)])
 POINT_DTYPE = np.dtype([("q", np.float32, 3), ("r", np.float32)])
 CLOSEST_DTYPE = np.dtype([("id", np.int32), ("d2", np.float32), ("u", np.float32), ("v", np.float32),
                           ("p", np.float32, 3), ("reserved", np.uint32)])
@@ -148,7 +153,8 @@ ABI_SYMBOLS = ["rt_create", "rt_upload_scene", "rt_set_params", "rt_render", "rt
                "rt_trace_rays_attr", "rt_trace_rays_attr_device",
                "rt_trace_fan", "rt_trace_fan_device", "rt_fan_expand",
                "rt_closest_points", "rt_closest_points_device", "rt_closest_points_host",
-               "rt_nearest_k", "rt_nearest_k_device", "rt_nearest_k_host"]
+               "rt_nearest_k", "rt_nearest_k_device", "rt_nearest_k_host",
+               "rt_trace_rays_k", "rt_trace_rays_k_device", "rt_trace_rays_k_host"]
 HOST_SYMBOLS = ["rt_mesh_create", "rt_mesh_destroy", "rt_mesh_view_get", "rt_mesh_set", "rt_mesh_load_obj",
                 "rt_mesh_load_dae", "rt_mesh_save_dae",
                 "rt_mesh_gen_cornell", "rt_mesh_gen_torus_knot", "rt_mesh_gen_heightfield", "rt_mesh_gen_random",
@@ -256,6 +262,9 @@ def lib() -> C.CDLL:
             "rt_nearest_k": (C.c_int, [vp, vp, C.c_int64, i32, u32, vp]),
             "rt_nearest_k_device": (C.c_int, [vp, vp, C.c_int64, i32, u32, vp, vp]),
             "rt_nearest_k_host": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, C.c_int64, i32, vp, vp]),
+            "rt_trace_rays_k": (C.c_int, [vp, vp, C.c_int64, i32, u32, vp]),
+            "rt_trace_rays_k_device": (C.c_int, [vp, vp, C.c_int64, i32, u32, vp, vp]),
+            "rt_trace_rays_k_host": (C.c_int, [vp, i32, vp, i32, vp, i32, vp, i32, vp, C.c_int64, i32, vp, vp]),
             "rt_bvh_build_lbvh": (C.c_int, [vp, i32, C.POINTER(vp)]),
             "rt_mesh_create": (vp, []),
             "rt_mesh_destroy": (None, [vp]),
@@ -447,6 +456,25 @@ def nearest_k_host(scene: "Scene", points, k: int, r=None, stats: bool = False):
     st = np.zeros(3, np.uint64)
     _check(lib().rt_nearest_k_host(_ptr(v), v.shape[0], _ptr(idx), idx.size, _ptr(nodes), nodes.shape[0], _ptr(refs),
                                    refs.size, _ptr(rec), rec.shape[0], k, _ptr(out), _ptr(st) if stats else None))
+    if stats:
+        return out, {"overflows": int(st[0]), "inner_visits": int(st[1]), "tri_tests": int(st[2])}
+    return out
+
+
+def trace_rays_k_host(scene: "Scene", origins, directions, k: int, tmax=None, stats: bool = False):
+    """rt_trace_rays_k_host: the definition of Renderer.trace_rays_k in host code (S_strict), over the
+    scene's arrays (HIT_UV_DTYPE (k, n)); no GPU.  `origins` may be packed RAY_DTYPE records (then
+    `directions` and `tmax` are ignored).  stats=True: also {overflows, inner_visits, tri_tests} of the call."""
+    rays = origins if getattr(origins, "dtype", None) == RAY_DTYPE else pack_rays(origins, directions, tmax)
+    rays = np.ascontiguousarray(rays)
+    v = np.ascontiguousarray(scene.vertices, dtype=np.float32).reshape(-1, 4)
+    idx = np.ascontiguousarray(scene.indices, dtype=np.int32)
+    nodes = np.ascontiguousarray(scene.nodes, dtype=np.float32).reshape(-1, 12)
+    refs = np.ascontiguousarray(scene.tri_indices, dtype=np.int32)
+    out = np.zeros((max(int(k), 0), rays.shape[0]), HIT_UV_DTYPE)
+    st = np.zeros(3, np.uint64)
+    _check(lib().rt_trace_rays_k_host(_ptr(v), v.shape[0], _ptr(idx), idx.size, _ptr(nodes), nodes.shape[0], _ptr(refs),
+                                      refs.size, _ptr(rays), rays.shape[0], k, _ptr(out), _ptr(st) if stats else None))
     if stats:
         return out, {"overflows": int(st[0]), "inner_visits": int(st[1]), "tri_tests": int(st[2])}
     return out
@@ -1105,6 +1133,26 @@ class Renderer:
         _check(lib().rt_trace_rays_attr_device(self._h, C.c_void_p(d_rays or None), n,
                                                flags | (RT_FLAG_ANY_HIT if any_hit else 0), C.c_void_p(d_hits or None),
                                                C.c_void_p(stream or None)), self._h)
+
+    def trace_rays_k(self, origins, directions, k: int, tmax=None, flags: int = 0) -> np.ndarray:
+        """rt_trace_rays_k: for each of n rays the first k (1..8) distinct triangles along it within
+        (0.001, tmax) -> HIT_UV_DTYPE (k, n), row j the j-th hit of every ray, ordered by (t, id), with
+        the barycentrics u, v of each hit; entries beyond the number found are the miss record (id -1,
+        t = the ray's tmax word, u = v = 0).  With k = 1 the t words are trace_rays' closest hit, which is
+        the faster call for one hit.  Rays as trace_rays'; `origins` may be packed RAY_DTYPE records.
+        flags: a math flag, RT_FLAG_EXACT_DIV."""
+        rays = origins if getattr(origins, "dtype", None) == RAY_DTYPE else pack_rays(origins, directions, tmax)
+        rays = np.ascontiguousarray(rays)
+        out = np.zeros((max(int(k), 0), rays.shape[0]), HIT_UV_DTYPE)
+        _check(lib().rt_trace_rays_k(self._h, _ptr(rays), rays.shape[0], k, flags, _ptr(out)), self._h)
+        return out
+
+    def trace_rays_k_device(self, d_rays: int, n: int, k: int, d_out: int, flags: int = 0, stream: Optional[int] = None) -> None:
+        """rt_trace_rays_k_device: n rt_ray at d_rays -> k planes of n rt_hit_uv at d_out (both 16-byte
+        aligned), enqueued on `stream` (None = the ctx's own); returns after enqueue."""
+        _stream_arg(stream)
+        _check(lib().rt_trace_rays_k_device(self._h, C.c_void_p(d_rays or None), n, k, flags, C.c_void_p(d_out or None),
+                                            C.c_void_p(stream or None)), self._h)
 
     def trace_fan(self, origins, directions, normals=None, tmax=None, flags: int = 0) -> np.ndarray:
         """rt_trace_fan: n origins against the same k directions, one occlusion bit per ray ->

@@ -8,7 +8,8 @@ SGPRs, scratch bytes per lane, LDS bytes, waves per SIMD.  Usage:
 The filter is a substring of the mangled name: `query_kernel` lists the plain ray query's
 instantiations, `query_attr_kernel` the attribute query's, `query_` both,
 `fan_kernel` the occlusion fan's, `closest_kernel` the closest-point query's,
-`nearest_kernel` the k-nearest-triangle query's eight.
+`nearest_kernel` the k-nearest-triangle query's eight, `multihit_kernel` the first-k-hits
+query's 24.
 """
 import os
 import re
